@@ -12,12 +12,18 @@ pdf / samples are gathered on rank 0 with one RCCL gather over xGMI per step, is
 asynchronously so it overlaps the next step's walk (N = 1: no collective).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5|anchor64|...]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
-Rank 0 prints one JSON line.  ``roofline`` prices the dominant kernel (vbn_walk_kernel) with
-HIP events on the stream it runs on; ``cpu_baseline`` times the CPU oracle (the reference's
-torch op sequence, oracle/vbn_oracle.py) on a bounded sample on this host's cores, in a
-fresh child process with the tuned glibc allocator settings of BASELINE.md.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline figures (``value``, ``ms_per_step``).  ``--dump-outputs DIR`` also writes the arrays the
+last timed step returned (``DIR/pdf.npy``, ``DIR/samples.npy``); the timed steps' seeds are fixed,
+so two builds run with the same arguments can be compared output for output.  ``--full`` adds
+the measurements that take runs of their own: ``roofline`` prices the dominant kernel
+(vbn_walk_kernel) with HIP events on the stream it runs on; ``gather`` (N > 1) prices the RCCL
+gather; ``cpu_baseline`` times the CPU oracle (the reference's torch op sequence,
+oracle/vbn_oracle.py) on a bounded sample on this host's cores, in a fresh child process with
+the tuned glibc allocator settings of BASELINE.md.
 """
 from __future__ import annotations
 
@@ -236,6 +242,43 @@ def load_traffic(cfg_name: str):
         return None, None
 
 
+TIMED_SEED = 2                    # base of the timed steps' seed stream (distributed.seed_stream)
+DUMP_BUDGET = 64 * 2 ** 20        # --dump-outputs: bytes written at most, over all arrays
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """``--dump-outputs``: write each array as ``out_dir/<name>.npy`` (float32 / float64).  Over
+    DUMP_BUDGET bytes in all, every array keeps the same fraction of its rows (dim 0: the
+    queries), picked by a fixed seed, so two runs keep the same rows.  Returns what was written:
+    {name: {"shape", "full_shape", "dtype"}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64 if a.dtype.kind in "iu" and a.dtype.itemsize > 2 else np.float32)
+        host[name] = a
+    total = sum(a.nbytes for a in host.values())
+    rng = np.random.default_rng(0)
+    written = {}
+    for name, a in host.items():
+        full_shape = list(a.shape)
+        if total > DUMP_BUDGET:
+            keep = DUMP_BUDGET / total
+            rows = a.shape[0] if a.ndim else 1
+            if a.ndim and int(rows * keep) >= 1:
+                a = a[np.sort(rng.permutation(rows)[: int(rows * keep)])]
+            else:                                     # fewer rows than the budget allows: flat sample
+                flat = a.reshape(-1)
+                a = flat[np.sort(rng.choice(flat.size, max(1, int(flat.size * keep)), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = {"shape": list(a.shape), "full_shape": full_shape, "dtype": str(a.dtype)}
+    return written
+
+
 KT_UNTIMED, KT_TIMED = 64, 20     # roofline kernel timing: untimed launches, then timed ones
 _T0 = time.perf_counter()
 
@@ -338,7 +381,12 @@ def main():
     ap.add_argument("--config", default="cfg4",
                     help="workload (vectorizedbayesiannetwork_amd/synthetic.py CONFIGS); default cfg4, the "
                          "largest single-GPU config of BASELINE.json (64-node KDE DAG, M = 10k, 4096 x 1024)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the walk kernel's roofline, the gather "
+                         "accounting (--gpus N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's pdf / samples as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-queries", type=int, default=0)
     ap.add_argument("--cpu-reps", type=int, default=5)
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
@@ -357,6 +405,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.no_precompute:
         from vectorizedbayesiannetwork_amd import engines as _E
         _E.PRECOMPUTE = False
@@ -370,7 +420,7 @@ def main():
         stub_main(args)
         return
 
-    from vectorizedbayesiannetwork_amd.distributed import ShardedEngine
+    from vectorizedbayesiannetwork_amd.distributed import ShardedEngine, seed_stream
     world, rank, local, device = init_ranks(args)
     dist = world > 1
     if dist:
@@ -418,33 +468,37 @@ def main():
     t_wait = time.perf_counter()
     jit.wait_pending()
     t_wait = time.perf_counter() - t_wait
+    t_second = time.perf_counter()
     vbn.infer_posterior(query)
     sharded.wait()
     torch.cuda.synchronize()
+    t_second = time.perf_counter() - t_second
     specialised = bool(ops.LAST_WALK.get("specialised"))
     last = dict(E.LAST_LAUNCH)
     pk, plan, fixed = last["pk"], last["plan"], last["fixed"]
-    stream = torch.cuda.current_stream()
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    log("kernel timing")
-    ev0.record(stream)
-    E.run_walk(pk, plan, fixed, B, S, seed=1000)
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    first_ms = max(ev0.elapsed_time(ev1), 1e-3)
-    # ~60 ms of untimed walks (the clock ramp: a 0.9-ms walk needs ~35 launches to reach its
-    # steady clock, profiles/r03_cfg2_kernel_trace), then >= 3 timed (~20 ms, at most 20)
-    untimed = max(2, min(KT_UNTIMED, math.ceil(60.0 / first_ms)))
-    reps = max(3, min(KT_TIMED, math.ceil(20.0 / first_ms)))
-    for i in range(untimed):
-        E.run_walk(pk, plan, fixed, B, S, seed=1001 + i)
-    ev0.record(stream)
-    for i in range(reps):
-        E.run_walk(pk, plan, fixed, B, S, seed=i + 2)
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = ev0.elapsed_time(ev1) / reps
-    assert bool(ops.LAST_WALK.get("specialised")) == specialised, "kernel timing ran another walk form"
+    kern_ms = reps = untimed = None
+    if args.full:
+        stream = torch.cuda.current_stream()
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        log("kernel timing")
+        ev0.record(stream)
+        E.run_walk(pk, plan, fixed, B, S, seed=1000)
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        first_ms = max(ev0.elapsed_time(ev1), 1e-3)
+        # ~60 ms of untimed walks (the clock ramp: a 0.9-ms walk needs ~35 launches to reach its
+        # steady clock, profiles/r03_cfg2_kernel_trace), then >= 3 timed (~20 ms, at most 20)
+        untimed = max(2, min(KT_UNTIMED, math.ceil(60.0 / first_ms)))
+        reps = max(3, min(KT_TIMED, math.ceil(20.0 / first_ms)))
+        for i in range(untimed):
+            E.run_walk(pk, plan, fixed, B, S, seed=1001 + i)
+        ev0.record(stream)
+        for i in range(reps):
+            E.run_walk(pk, plan, fixed, B, S, seed=i + 2)
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = ev0.elapsed_time(ev1) / reps
+        assert bool(ops.LAST_WALK.get("specialised")) == specialised, "kernel timing ran another walk form"
     kernel_name = "vbn_walk_plan" if specialised else "vbn_walk_kernel"
     precomputed = bool(E.LAST_LAUNCH.get("precomputed"))
     n_pre_s = n_pre_q = 0
@@ -461,9 +515,14 @@ def main():
     # the host path's own settling (caching allocator, Python-side caches) before the W warmup
     # steps: ~50 ms of untimed infer_posterior calls, like the walks of the kernel timing above
     # (a 20-step window right after a handful of calls measured 0.92 vs 0.82 ms per step in
-    # steady state, profiles/r03_bench/r03t_blocks.txt)
-    log(f"kernel {kern_ms:.4f} ms; settling calls")
-    n_settle = max(5, min(200, math.ceil(50.0 / kern_ms)))
+    # steady state, profiles/r03_bench/r03t_blocks.txt).  Without --full there is no kernel
+    # timing before them: they are sized by the second call and also cover its ~60 ms clock ramp
+    if args.full:
+        log(f"kernel {kern_ms:.4f} ms; settling calls")
+        n_settle = max(5, min(200, math.ceil(50.0 / kern_ms)))
+    else:
+        log(f"second call {1e3 * t_second:.4f} ms; settling calls")
+        n_settle = max(5, min(200 + KT_UNTIMED, math.ceil(110.0 / max(1e3 * t_second, 1e-3))))
     if dist:
         # every call gathers (a collective): all ranks must make the same number of calls, and
         # their kernel times differ (the max keeps the slowest rank's ~50 ms)
@@ -488,6 +547,9 @@ def main():
     # its clocks drop (0.976 vs 0.813 ms per step over the driver's 20 steps)
     log("timed region")
     sharded.verify = False
+    # the timed steps draw their seeds from a stream restarted here (the same on every rank), so
+    # their outputs do not depend on how many untimed calls came before (--dump-outputs)
+    sharded._gen = seed_stream(TIMED_SEED)
     gc.disable()
     barrier()
     torch.cuda.synchronize()
@@ -511,10 +573,15 @@ def main():
     if rank == 0 and gather:
         assert pdf is not None and pdf.shape[0] == world * B, "rank 0 must hold the gathered batch"
 
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        log(f"writing the last step's outputs to {args.dump_outputs}")
+        dumped = dump_outputs(args.dump_outputs, {"pdf": pdf, "samples": samples})
+
     # the gather's cost, outside the timed region: the same steps with no gather and with a
     # synchronous (not overlapped) gather, max over ranks; rank 0's received bytes per step
     gather_info = None
-    if dist and gather:
+    if args.full and dist and gather:
         def window(n, on, overlap):
             sharded.gather, sharded.overlap = on, overlap
             barrier()
@@ -543,42 +610,44 @@ def main():
                        "overlapped_ms_per_step": round(ms_per_step, 4),
                        "steps_each": n_g}
 
-    f32_fl, hid_fl = mlp_flops_per_particle(model, plan)
-    f32_fl, hid_fl = f32_fl * B * S, hid_fl * B * S
-    flops = f32_fl + hid_fl
-    exact = bool(getattr(engine, "exact_f32", False))
-    hid_peak = FP32_PEAK_TFLOPS if exact else F16_PEAK_TFLOPS / SPLIT_PASSES
-    exps = kde_exps_per_particle(model, plan) * B * S
-    traffic, traffic_src = load_traffic(args.config)
-    kern_s = kern_ms * 1e-3
-    ex_f32, ex_hid, ex_exps = executed_work(model, plan, B, S, precomputed)
-    ex_flops = ex_f32 + ex_hid
-    if exps > 0.1 * flops / 64:
-        # KDE: one exp per (particle, point) kernel weight; the bound is the v_exp_f32 issue rate
-        ach = exps / kern_s / 1e12
-        roof = {"bound": "exp", "achieved": round(ach, 4), "peak": round(EXP_PEAK_T, 2), "unit": "Texp/s",
-                "frac": round(ach / EXP_PEAK_T, 4), "traffic": traffic, "kernel": kernel_name,
-                "kernel_ms": round(kern_ms, 4), "exps_per_launch": exps,
-                "peak_basis": "v_exp_f32 issue: 8 cyc per wave64 per SIMD, 1024 SIMDs, 2.4 GHz",
-                "executed_exps_per_launch": ex_exps,
-                "executed_frac": round(ex_exps / kern_s / 1e12 / EXP_PEAK_T, 4),
-                "launches_timed": reps, "launches_untimed_before": untimed + 1}
-    else:
-        # blended peak: each FLOP class at the dense peak of the unit that runs it
-        t_min = f32_fl / (FP32_PEAK_TFLOPS * 1e12) + hid_fl / (hid_peak * 1e12)
-        peak = flops / t_min / 1e12
-        achieved = flops / kern_s / 1e12
-        roof = {"bound": "mfma", "achieved": round(achieved, 3), "peak": round(peak, 1), "unit": "TFLOP/s",
-                "frac": round(achieved / peak, 4), "traffic": traffic,
-                "kernel": kernel_name, "kernel_ms": round(kern_ms, 4), "flops_per_launch": flops,
-                "hidden_layer": "f32 MFMA" if exact else "split-f16 MFMA (3 pass, f32 accumulate)",
-                "peak_basis": f"f32 FLOPs at {FP32_PEAK_TFLOPS} TF, hidden-layer FLOPs at {hid_peak:.1f} TF",
-                "f32_equiv_frac_of_fp32_peak": round(achieved / FP32_PEAK_TFLOPS, 4),
-                "executed_flops_per_launch": ex_flops,
-                "executed_frac": round(ex_flops / kern_s / 1e12 /
-                                       (ex_flops / (ex_f32 / (FP32_PEAK_TFLOPS * 1e12) + ex_hid / (hid_peak * 1e12)) / 1e12), 4),
-                "launches_timed": reps, "launches_untimed_before": untimed + 1}
-    roof["traffic_source"] = traffic_src
+    roof = None
+    if args.full:
+        f32_fl, hid_fl = mlp_flops_per_particle(model, plan)
+        f32_fl, hid_fl = f32_fl * B * S, hid_fl * B * S
+        flops = f32_fl + hid_fl
+        exact = bool(getattr(engine, "exact_f32", False))
+        hid_peak = FP32_PEAK_TFLOPS if exact else F16_PEAK_TFLOPS / SPLIT_PASSES
+        exps = kde_exps_per_particle(model, plan) * B * S
+        traffic, traffic_src = load_traffic(args.config)
+        kern_s = kern_ms * 1e-3
+        ex_f32, ex_hid, ex_exps = executed_work(model, plan, B, S, precomputed)
+        ex_flops = ex_f32 + ex_hid
+        if exps > 0.1 * flops / 64:
+            # KDE: one exp per (particle, point) kernel weight; the bound is the v_exp_f32 issue rate
+            ach = exps / kern_s / 1e12
+            roof = {"bound": "exp", "achieved": round(ach, 4), "peak": round(EXP_PEAK_T, 2), "unit": "Texp/s",
+                    "frac": round(ach / EXP_PEAK_T, 4), "traffic": traffic, "kernel": kernel_name,
+                    "kernel_ms": round(kern_ms, 4), "exps_per_launch": exps,
+                    "peak_basis": "v_exp_f32 issue: 8 cyc per wave64 per SIMD, 1024 SIMDs, 2.4 GHz",
+                    "executed_exps_per_launch": ex_exps,
+                    "executed_frac": round(ex_exps / kern_s / 1e12 / EXP_PEAK_T, 4),
+                    "launches_timed": reps, "launches_untimed_before": untimed + 1}
+        else:
+            # blended peak: each FLOP class at the dense peak of the unit that runs it
+            t_min = f32_fl / (FP32_PEAK_TFLOPS * 1e12) + hid_fl / (hid_peak * 1e12)
+            peak = flops / t_min / 1e12
+            achieved = flops / kern_s / 1e12
+            roof = {"bound": "mfma", "achieved": round(achieved, 3), "peak": round(peak, 1), "unit": "TFLOP/s",
+                    "frac": round(achieved / peak, 4), "traffic": traffic,
+                    "kernel": kernel_name, "kernel_ms": round(kern_ms, 4), "flops_per_launch": flops,
+                    "hidden_layer": "f32 MFMA" if exact else "split-f16 MFMA (3 pass, f32 accumulate)",
+                    "peak_basis": f"f32 FLOPs at {FP32_PEAK_TFLOPS} TF, hidden-layer FLOPs at {hid_peak:.1f} TF",
+                    "f32_equiv_frac_of_fp32_peak": round(achieved / FP32_PEAK_TFLOPS, 4),
+                    "executed_flops_per_launch": ex_flops,
+                    "executed_frac": round(ex_flops / kern_s / 1e12 /
+                                           (ex_flops / (ex_f32 / (FP32_PEAK_TFLOPS * 1e12) + ex_hid / (hid_peak * 1e12)) / 1e12), 4),
+                    "launches_timed": reps, "launches_untimed_before": untimed + 1}
+        roof["traffic_source"] = traffic_src
 
     par = f"query-sharded dp{world}" + (" + one RCCL gather of pdf/samples to rank 0 per step (async, "
                                         "overlapping the next walk)" if gather and dist else "")
@@ -607,13 +676,16 @@ def main():
                    "precompute_nodes": {"per_sample": n_pre_s, "per_query": n_pre_q},
                    "kde_moment_nodes": int(sum(1 for r in plan.steps.tolist()
                                                if r[0] == KIND_ID["kde"] and r[1] == 1 and r[31] >= 0))},
-        "roofline": roof,
     }
+    if roof is not None:
+        out["roofline"] = roof
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if fallbacks:
         out["config"]["is_fallback_steps"] = sum(fallbacks)
     if gather_info is not None:
         out["gather"] = gather_info
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # a bounded sample of ~10-30 s of CPU work (the oracle's q/s is linear in B): cfg2 /
         # anchor64 1024 queries, cfg3 (IS, ~100 q/s) 256, cfg5 (~0.7 q/s) 4, cfg4 (~0.2 q/s) 1;
         # KDE configs time 3 repetitions after the warm-up (~5 s each), the others 5

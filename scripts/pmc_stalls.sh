@@ -9,7 +9,7 @@ tag=$1; lib=${2:-}; cfg=${3:-cfg2}
 out=gpurun_out/stalls_$tag
 mkdir -p $out
 [ -n "$lib" ] && export VBN_HIP_LIB=$(readlink -f $lib)
-B="bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline"
+B="bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline"
 passes=(
   "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS"
   "SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM_RD SQ_INST_LEVEL_SMEM SQ_INSTS_SMEM SQ_INST_LEVEL_LDS SQ_INSTS_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_VALU_MFMA_COEXEC_CYCLES"

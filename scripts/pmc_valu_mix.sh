@@ -4,7 +4,7 @@
 set -o pipefail
 export TMPDIR=/tmp
 for c in "$@"; do
-  B="bench.py --config $c --steps 5 --warmup 1 --no-cpu-baseline"
+  B="bench.py --full --config $c --steps 5 --warmup 1 --no-cpu-baseline"
   timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_CVT SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_INT64 --output-format csv -d gpurun_out/mix_$c/p1 -o run -- python3 $B > gpurun_out/mix_$c.p1.log 2>&1 || exit $?
   timeout -s KILL 120 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_INST_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_SALU SQ_ACTIVE_INST_ANY --output-format csv -d gpurun_out/mix_$c/p2 -o run -- python3 $B > gpurun_out/mix_$c.p2.log 2>&1 || exit $?
   python3 - "$c" <<'PY'

@@ -3,7 +3,8 @@
 hiprtc) into the package's plan cache (vectorizedbayesiannetwork_amd/plan_cache), so a fresh
 GPU box loads them instead of compiling inside the first call.
 
-    python scripts/precompile_plans.py [cfg2 cfg3 ...]        (default: every bench config)
+    python scripts/precompile_plans.py [cfg2 cfg3 ...]        (default: --bench, every bench config;
+                                                               --tests: the GPU tests' extra plans)
 
 Per config: the bench engine's production plan (MCM / IS / LW) and, for shared-root engines,
 its shared-sample precompute variant (plan.precompute_plans) -- the same step tables the
@@ -59,11 +60,23 @@ def plans_for(name):
     return cfg, out
 
 
-def _one(name):
+BENCH = ["cfg2", "cfg3", "cfg4", "cfg5", "anchor64"]
+# the extra plans of the GPU tests' workloads
+TESTS = ["cfg2:is", "cfg2:lw", "cfg3:lw", "cfg3:mcm", "cfg3:ancestral", "cfg4:lw", "cfg4:ancestral",
+         "cfg5:lw", "cfg5:ancestral"]
+TAGS = ("plain", "precompute")
+
+
+def _one(task):
+    """One plan of one workload: (name, tag).  The precompute variant of a workload without one
+    gives no line."""
     from vectorizedbayesiannetwork_amd import jit
+    name, want = task
     cfg, plans = plans_for(name)
     lines = []
     for tag, plan, pre in plans:
+        if tag != want:
+            continue
         t0 = time.perf_counter()
         key, comp = jit.precompile(plan, cfg["B"], cfg["S"], precomp=pre)
         lines.append(f"{name} {tag}: {key} ({'compiled' if comp else 'cached'} in {time.perf_counter() - t0:.1f} s)")
@@ -71,20 +84,24 @@ def _one(name):
 
 
 def main(names):
-    from concurrent.futures import ProcessPoolExecutor
+    from concurrent.futures import ProcessPoolExecutor, as_completed
     from vectorizedbayesiannetwork_amd import synthetic
-    names = names or ["cfg2", "cfg3", "cfg4", "cfg5", "anchor64"]
-    if names == ["--tests"]:                 # the extra plans of the GPU tests' workloads
-        names = ["cfg2:is", "cfg2:lw", "cfg3:lw", "cfg3:mcm", "cfg3:ancestral", "cfg4:lw", "cfg4:ancestral",
-                 "cfg5:lw", "cfg5:ancestral"]
+    expanded = []
+    for name in names or ["--bench"]:        # --bench / --tests may stand among config names
+        expanded += BENCH if name == "--bench" else TESTS if name == "--tests" else [name]
+    names = list(dict.fromkeys(expanded))
     for name in names:
         if name.partition(":")[0] not in synthetic.CONFIGS or name.partition(":")[2] not in ("", *ENGINES):
             raise SystemExit(f"unknown config {name}")
-    # one hiprtc compile per process at a time (single-threaded, ~1-2 GB each)
-    workers = max(1, min(len(names), (os.cpu_count() or 1), 8))
+    # one task per plan, not per workload (a 128-node plan compiles for minutes, and a workload's
+    # two plans need not wait for each other), the workloads with most nodes first; one hiprtc
+    # compile per process at a time (single-threaded, ~1-2 GB each)
+    names.sort(key=lambda n: -synthetic.CONFIGS[n.partition(":")[0]]["n_nodes"])
+    tasks = [(name, tag) for name in names for tag in TAGS]
+    workers = max(1, min(len(tasks), (os.cpu_count() or 1), 8))
     with ProcessPoolExecutor(workers) as ex:
-        for lines in ex.map(_one, names):
-            for ln in lines:
+        for fut in as_completed([ex.submit(_one, t) for t in tasks]):
+            for ln in fut.result():
                 print(ln, flush=True)
 
 
