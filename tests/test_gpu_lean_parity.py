@@ -48,6 +48,13 @@ LW_ATOL = 1e-4
 # differed (cfg4, M = 10,000 points per draw) had its smallest margin at 6e-10 .. 6e-9, 20-200x
 # inside this bound, while 6-7 % of cfg4's particles carry a draw inside it (round 5's fixed
 # 1e-5 flagged 99.8 %).
+# This figure counts partial-sum rounding alone.  The per-particle bound derived stage by stage
+# (operand and a' rounding, v_exp_f32, the chunk sums, the scan) is tests/kde_reference.margin:
+# a few 1e-6 for KDE nodes on the MFMA pass at M = 10,000, and KDE nodes whose pass 1 comes from
+# a moment table carry the table's row bound on top (4e-7 per row, tests/test_kde_moments.py),
+# itself larger than TIE -- so a flip on such a node with its margin between TIE and that bound
+# would be legitimate and would still be reported here as unexplained.  None has been seen;
+# tests/test_gpu_kde_paths.py judges KDE choices against the derived bound, particle by particle.
 TIE = 2.0 ** -23
 # (B, S) of the per-particle comparisons: sizes the oracle finishes in seconds (cfg4's MCM runs
 # 8 queries, its other engines 2)

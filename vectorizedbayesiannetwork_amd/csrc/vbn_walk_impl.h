@@ -1518,6 +1518,13 @@ __device__ __forceinline__ void kde_b32_sums(const bf16x8* __restrict__ pa, int 
 // KDE_FFORM_MAX (no overflow: sums <= M 2^{|x'|^2}); otherwise the full form.
 #define KDE_FFORM_MAX 96.f
 
+// v_exp_f32 gives 0 for results below 2^-126 (no denormal results), so a sum of M weights whose
+// largest lies near 2^-126 has silently lost up to M 2^-126 of its mass while still being > 0
+// (measured: a log-density 0.058 too low where the sum was ~2^-123, tests/test_gpu_kde_paths.py).
+// Below kde_tiny(M) = M 2^-109 -- where that loss could exceed 2^-17 of the sum -- a sum counts
+// as underflowed, exactly like a sum of 0: the rescue / the shifted path takes the particle.
+__device__ __forceinline__ float kde_tiny(int M) { return (float)M * 0x1p-109f; }
+
 // Sub-chunks (round 6; VBN_ABL_NOHALVES: A/B without).  A wave's scan lasts as long as its
 // slowest lane's, about half a chunk (the max over 64 lanes of the bidirectional walk).  Pass 1
 // therefore also keeps KDE_NSUB - 1 prefix sums per chunk (a private array: the LDS rows are
@@ -1787,7 +1794,7 @@ __device__ __forceinline__ int kde_index_mfma(const vbn_walk_args& A, const vbn_
   }
   const int nfr = nf;                                 // replica form of the pass-1 elements
   const float xb0 = 2.f * xv[0], xb1 = 2.f * xv[1], xb2 = 2.f * xv[2];
-  if (!pre && !(tot > 0.0)) {                         // every weight underflowed (or NaN parent)
+  if (!pre && !(tot >= (double)kde_tiny(M))) {       // the weights underflowed (or NaN parent)
     halves = false;
     float amax = -INFINITY;
     for (int j = 0; j < M; ++j) amax = fmaxf(amax, kde_arg_rec(rec[j], xb0, xb1, xb2, 0.f, nfr));
@@ -1868,7 +1875,7 @@ __device__ __forceinline__ int kde_index_mfma(const vbn_walk_args& A, const vbn_
 //   root:     LSE_j log K_y - log M
 //   non-root: LSE_j (log K_p + log K_y) - LSE_j log K_p
 // pack kq (parent features) and kqy (parent ++ target features, scales c_p / c_y).  Returns
-// false (nothing added) when a sum underflows; the caller then takes the shifted VALU path.
+// false (nothing added) when a sum underflows (kde_tiny); the caller then takes the shifted VALU path.
 __device__ __forceinline__ bool kde_logp_mfma(const vbn_step& st, const Lane& L, bool root, float c_p,
                                               float c_y, float cy, float log_n, float& lp, float lsp) {
   const int M = st.k, dp = st.aux0, D = st.out_dim, lane = L.lane;
@@ -1895,7 +1902,7 @@ __device__ __forceinline__ bool kde_logp_mfma(const vbn_step& st, const Lane& L,
   // particle)
   if (!root && __all(lsp == lsp)) {
     wave_sync();
-    if (!(sy > 0.f)) return false;
+    if (!(sy >= kde_tiny(M))) return false;
     lp += ((__logf(sy) - (fform ? sq_y * LN2 : 0.f)) - lsp) + cy;
     return true;
   }
@@ -1906,7 +1913,7 @@ __device__ __forceinline__ bool kde_logp_mfma(const vbn_step& st, const Lane& L,
     sp = kde_sums_nf(pa, nb32, L, slots, scl, dp, fform);
   }
   wave_sync();
-  if (!(sy > 0.f) || !(sp > 0.f)) return false;
+  if (!(sy >= kde_tiny(M)) || !(sp >= kde_tiny(M))) return false;
   const float corr = fform ? (root ? sq_y : sq_y - sq_p) * LN2 : 0.f;
   lp += root ? ((__logf(sy) - corr) + cy - log_n) : (((__logf(sy) - __logf(sp)) - corr) + cy);
   return true;
@@ -1972,7 +1979,7 @@ __device__ __forceinline__ int kde_index_valu(const vbn_walk_args& A, const vbn_
   // per-point records (4 weight-0 rows before the first point), then the reversed copy
   const float4* __restrict__ rec = reinterpret_cast<const float4*>(L.P + st.reserved[3]) + 4;
   float shift = 0.f;
-  if (!(tot > 0.0)) {                                 // every weight underflowed (or NaN parent)
+  if (!(tot >= (double)kde_tiny(M))) {               // the weights underflowed (or NaN parent)
     float amax = -INFINITY;
     for (int j = 0; j < M; ++j) amax = fmaxf(amax, kde_arg_valu<NF>(xv, rec[j]));
     shift = amax;
@@ -2047,7 +2054,7 @@ __device__ __forceinline__ void step_kde_t(const vbn_walk_args& A, const vbn_ste
         tot += (double)cs;
       }
       float shift = 0.f;
-      if (!(tot > 0.0)) {                                 // all weights underflowed
+      if (!(tot >= (double)kde_tiny(M))) {               // the weights underflowed
         shift = qmin;
         tot = 0.0;
         for (int ch = 0; ch < KDE_CHUNKS; ++ch) {
@@ -2108,7 +2115,7 @@ __device__ __forceinline__ void step_kde_t(const vbn_walk_args& A, const vbn_ste
       }
     }
     float sh_y = 0.f, sh_p = 0.f;
-    if (!(sy > 0.f) || (!root && !(sp > 0.f))) {   // underflow: re-sum relative to the minimum
+    if (!(sy >= kde_tiny(M)) || (!root && !(sp >= kde_tiny(M)))) {   // underflow: re-sum relative to the minimum
       sh_y = root ? qymin : qsmin;
       sh_p = qpmin;
       sy = 0.f;
