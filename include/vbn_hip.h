@@ -23,6 +23,12 @@
  *                             MDNCPD          (vbn/cpds/mdn.py:185-272)
  *                             KDECPD          (vbn/cpds/kde.py:105-182)
  *                             SoftmaxNNCPD    (vbn/cpds/softmax_nn.py:581-759).
+ *   vbn_hip_table_walk      (ABI v14) the same topological particle pass for networks whose every
+ *                           CPD is a CategoricalTableCPD: _logits_from_parents / sample /
+ *                           log_prob (vbn/cpds/categorical_table.py:359-417) as gathers from
+ *                           per-configuration log-prob and inverse-CDF rows the host packs, and,
+ *                           through a PARAMS walk at S = 1, the probability row of
+ *                           CategoricalExact.infer_posterior (vbn/inference/categorical_exact.py:89-128)
  *   vbn_hip_posterior_stats VBN._posterior_stats (vbn/vbn.py:483-504), the summary behind
  *                             VBN.infer_relative (vbn/vbn.py:519-568); fused forms (ABI v13):
  *                             the MCM walk's epilogue partials (vbn_walk_args.stats_part) +
@@ -53,7 +59,7 @@
 extern "C" {
 #endif
 
-#define VBN_ABI_VERSION 13
+#define VBN_ABI_VERSION 14
 
 /* error codes besides hipError_t values */
 #define VBN_E_ARGS 1001
@@ -66,6 +72,23 @@ int vbn_hip_struct_size(int which);
 
 /* Topological particle walk (see header comment). */
 int vbn_hip_walk(const vbn_walk_args* args, void* stream);
+
+/* (ABI v14) The walk for plans whose every step is a categorical_table (kind 5, kind_mask 1024;
+ * csrc/vbn_table_walk.hip).  Same argument struct: modes MCM / WEIGHTED / SAMPLE, roles LATENT /
+ * FIXED / PARAMS / SKIP, flags LOGP / ROOT / SHARED / CLAMP_EV, fixed_per_particle, injected
+ * noise (slot 0 = the categorical uniform), run_if, q_base, out_lp, out_x (class VALUES).
+ * Node slots hold class indices; out_cols is [n_out_cols slots] ++ [n_out_cols blob offsets of
+ * the columns' class values, -1 for a PARAMS column]; wbuf_floats is the length of the parameter
+ * blob in floats (a multiple of 256), which the launch stages into LDS when that does not cut
+ * occupancy (environment VBN_TABLE_GLOBAL=1: never).  VBN_E_ARGS for what it does not implement:
+ * state / state_flags, precomp_q, stats_part, wave_particles = 32, mode GIBBS, any other
+ * kind_mask; vbn_hip_walk in turn refuses kind_mask 1024.  (Replaces
+ * vbn/cpds/categorical_table.py:359-417 inside the engines' topological loops and
+ * vbn/inference/categorical_exact.py:89-128.) */
+int vbn_hip_table_walk(const vbn_walk_args* args, void* stream);
+/* 1 when vbn_hip_table_walk would stage these arguments' tables into LDS, 0 when it gathers
+ * them from global memory, -(error code) for arguments it refuses. */
+int vbn_hip_table_walk_staged(const vbn_walk_args* args);
 
 /* The kind-set instantiation (walk_inst.hip / VBN_WALK_KIND_SETS: CPD kinds | 64 half-wave |
  * 128 lean | 256 half-wave without injected draws | 512 generic MLP) vbn_hip_walk would launch

@@ -21,7 +21,8 @@ enum vbn_kind {
   VBN_KIND_LINEAR_GAUSSIAN = 1,
   VBN_KIND_MDN = 2,
   VBN_KIND_KDE = 3,
-  VBN_KIND_SOFTMAX_NN = 4
+  VBN_KIND_SOFTMAX_NN = 4,
+  VBN_KIND_CATEGORICAL_TABLE = 5  /* walked by vbn_hip_table_walk only (csrc/vbn_table_walk.hip) */
 };
 
 /* role of a node for one query signature */
@@ -32,7 +33,7 @@ enum vbn_role {
   VBN_ROLE_PARAMS = 3,  /* write the CPD's conditional parameters, no draw (RB target,
                            CPDHandle.conditional, vbn/core/cpd_handle.py:40-118):
                            gaussian_nn / linear_gaussian: loc[D] ++ scale[D];
-                           softmax_nn: class probabilities[D][C];
+                           softmax_nn / categorical_table: class probabilities[D][C];
                            mdn: softmax(logits)[K] ++ loc[K][D] ++ scale[K][D]           */
   VBN_ROLE_SELECT = 4,  /* Gibbs: softmax over the 8 candidate lanes of a chain, choose one,
                            broadcast its value (out_col, out_dim) to the chain's lanes     */
@@ -136,7 +137,9 @@ typedef struct vbn_walk_args {
   int32_t n_out_cols;
   int32_t mode;            /* enum vbn_mode                                        */
   int32_t kind_mask;       /* CPD kinds walked: 1<<kind, | 32 if a non-relu activation,
-                              | 512 if some NN CPD has hidden_dims other than (32, 32) */
+                              | 512 if some NN CPD has hidden_dims other than (32, 32);
+                              1024 alone: every step is a categorical_table
+                              (vbn_hip_table_walk; vbn_hip_walk refuses it)             */
   int64_t q_base;          /* global index of query 0 (multi-GPU shards)            */
   uint64_t seed;
   uint64_t offset;         /* RNG stream offset (one per engine call)               */

@@ -12,13 +12,15 @@ import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VBN_HIP_LIB", os.path.join(HERE, "libvbn_hip.so"))
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 # exported symbols declared in include/vbn_hip.h
 EXPORTS = (
     "vbn_hip_abi_version",
     "vbn_hip_last_error",
     "vbn_hip_walk",
+    "vbn_hip_table_walk",
+    "vbn_hip_table_walk_staged",
     "vbn_hip_normalize_weights",
     "vbn_hip_normalize_weights_ex",
     "vbn_hip_rb_epilogue",
@@ -109,6 +111,10 @@ def load(path: str = None) -> ctypes.CDLL:
         lib.vbn_hip_last_error.restype = ctypes.c_char_p
         lib.vbn_hip_walk.argtypes = [ctypes.POINTER(VbnWalkArgs), ctypes.c_void_p]
         lib.vbn_hip_walk.restype = ctypes.c_int
+        lib.vbn_hip_table_walk.argtypes = [ctypes.POINTER(VbnWalkArgs), ctypes.c_void_p]
+        lib.vbn_hip_table_walk.restype = ctypes.c_int
+        lib.vbn_hip_table_walk_staged.argtypes = [ctypes.POINTER(VbnWalkArgs)]
+        lib.vbn_hip_table_walk_staged.restype = ctypes.c_int
         lib.vbn_hip_normalize_weights.argtypes = [
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32,
             ctypes.c_int32, ctypes.c_float, ctypes.c_void_p]

@@ -43,6 +43,7 @@ _ENGINE_DEFAULTS = {
                                               "min_scale": 1e-6, "fallback": "likelihood_weighting"},
         "resampled_importance_sampling": {"n_samples": 1024, "ess_threshold": 0.5, "resample": True,
                                           "clamp_obs": True},
+        "categorical_exact": {"fallback": "likelihood_weighting"},
     },
     "sampling": {"ancestral": {"n_samples": 512},
                  "gibbs": {"n_samples": 512, "burn_in": 50, "n_steps": 5}},
@@ -318,6 +319,9 @@ class VBN:
                   "likelihood_weighting": "is_lw", "ancestral": "ancestral"}
         if method not in ops_of:
             raise ValueError(f"pack_query: method must be one of {sorted(ops_of)}")
+        if any(rec.kind == "categorical_table" for rec in self.model.cpds.values()):
+            raise NotImplementedError("pack_query is not implemented for categorical_table networks: their walk "
+                                      "has no packed-plan form yet (use infer_posterior / sample)")
         names = {k: list(signature.get(k) or []) for k in ("evidence", "do")}
         q = self._normalize_query({"target": signature.get("target"),
                                    "evidence": {n: torch.zeros(1, self.model.out_dim(n)) for n in names["evidence"]},

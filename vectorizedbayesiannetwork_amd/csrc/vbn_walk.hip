@@ -608,6 +608,9 @@ static int fail(int code, const char* msg) {
   return code;
 }
 
+// the same for the other translation units of the library (vbn_table_walk.hip)
+int vbn_fail(int code, const char* msg) { return fail(code, msg); }
+
 extern "C" int vbn_hip_abi_version(void) { return VBN_ABI_VERSION; }
 extern "C" int vbn_hip_struct_size(int which) {
   return which == 0 ? (int)sizeof(vbn_walk_args) : (which == 1 ? (int)sizeof(vbn_step) : -1);
@@ -634,6 +637,8 @@ static int walk_shape(const vbn_walk_args* a, walk_launch* out) {
     return fail(VBN_E_ARGS, "vbn_hip_walk: bad arguments");
   if (a->out_x && (!a->out_cols || a->n_out_cols <= 0))
     return fail(VBN_E_ARGS, "vbn_hip_walk: out_x without out_cols");
+  if ((unsigned)a->kind_mask & ~1023u)
+    return fail(VBN_E_ARGS, "vbn_hip_walk: categorical_table plans (kind_mask 1024) run on vbn_hip_table_walk");
   if ((a->state_flags & 4) && (!a->state || a->state_flags != 4 || a->noise || a->mode == VBN_MODE_GIBBS))
     return fail(VBN_E_ARGS, "vbn_hip_walk: state_flags 4 (precomputed per-sample quantities) needs a state "
                             "buffer and a walk without injected draws, segments or Gibbs sweeps");

@@ -57,6 +57,7 @@ __all__ = [
     "AncestralSampler",
     "RaoBlackwellizedMarginalization",
     "ResampledImportanceSampling",
+    "CategoricalExact",
     "infer_batch_size",
 ]
 
@@ -118,6 +119,11 @@ def _plan(pk: PackedModel, key, **kw) -> QueryPlan:
     p = pk.model._cache.get(ck)
     if p is None:
         p = build_plan(pk, **kw)
+        if p.tabular:
+            # categorical_table plans walk the model's topological order (the log-weights add in
+            # the reference's order) and have nothing to precompute
+            pk.model._cache[ck] = p
+            return p
         if LIVENESS_ORDER and key[0] in _ORDERED and not kw.get("params") and _lds_bound(p):
             # the wave's LDS (value slots + scratch rows) limits the waves per CU: walk the DAG
             # in an order that keeps fewer values live (same draws, keyed by node; plan.py
@@ -229,6 +235,33 @@ def _check_discrete(pk: PackedModel, vals: Dict[str, torch.Tensor], nodes: Seque
         match = (v.unsqueeze(-1) == cv.unsqueeze(0)).any(-1)
         if bool(((~match) & disc.to(v.device).unsqueeze(0)).any()):
             raise ValueError("Found values outside discrete class set.")
+
+
+def _no_tables(vbn, what: str) -> None:
+    """Engines the table walk does not serve yet (follow-ups: they need segment state, the RB
+    epilogue or Gibbs sweeps in csrc/vbn_table_walk.hip); raised before anything touches the GPU."""
+    if any(rec.kind == "categorical_table" for rec in model_from_vbn(vbn).cpds.values()):
+        raise NotImplementedError(f"{what} is not implemented for categorical_table networks")
+
+
+def _check_table_support(pk: PackedModel, plan: QueryPlan, fixed: torch.Tensor) -> None:
+    """categorical_table.py:12-20 before the launch: every fixed value the walk maps to a class
+    index (plan.table_check) must be one of the node's valid class values -- which are also its
+    children's parent supports (model._check_table_model) -- else the reference's ValueError.
+    Likelihood weighting's clamped evidence is clamped first (_core.py:112-114).  One host sync."""
+    bad = None
+    for node, col, clamp in plan.table_check or ():
+        rec = pk.model.cpds[node]
+        cv, mask = rec.state["_class_values"], rec.state["_class_mask"].bool()
+        for d in range(int(rec.output_dim)):
+            v = fixed[:, col + d]
+            if clamp:
+                v = torch.nan_to_num(v, nan=0.0, posinf=1e6, neginf=-1e6).clamp(min=-1e6, max=1e6)
+            support = cv[d][mask[d]].to(device=v.device, dtype=torch.float32)
+            miss = ~(v.unsqueeze(-1) == support).any(-1).all()
+            bad = miss if bad is None else (bad | miss)
+    if bad is not None and bool(bad):
+        raise ValueError("Found values outside support.")
 
 
 def _next_seed() -> int:
@@ -369,6 +402,11 @@ def run_walk(pk: PackedModel, plan: QueryPlan, fixed: torch.Tensor, b: int, n: i
     # plain plan: its pre-passes would be two more launches of no-op waves on every call
     use_pc = (PRECOMPUTE and plan.pc is not None and noise is None and state is None and step_begin == 0
               and step_end < 0 and n % 64 == 0 and not fixed_per_particle and run_if is None)
+    if plan.tabular:
+        return _run_table_walk(pk, plan, fixed, b, n, seed=seed, offset=offset, q_base=q_base, noise=noise,
+                               noise_b=noise_b, fixed_per_particle=fixed_per_particle, state=state,
+                               run_if=run_if, out_x=out_x, stats_part=stats_part, step_begin=step_begin,
+                               step_end=step_end)
     pcs = _pc_state()
     if pcs["on"]:
         # VBN.precompile / pack_query: compile (or load) the specialised walk this launch would
@@ -463,6 +501,40 @@ def run_walk(pk: PackedModel, plan: QueryPlan, fixed: torch.Tensor, b: int, n: i
     return lp, x
 
 
+def _run_table_walk(pk, plan, fixed, b, n, *, seed, offset, q_base, noise, noise_b, fixed_per_particle, state,
+                    run_if, out_x, stats_part, step_begin, step_end):
+    """run_walk for a tabular plan: one vbn_hip_table_walk launch (no generations, pre-passes or
+    plan-specialised modules; in precompile mode there is nothing to compile)."""
+    if state is not None or stats_part is not None or step_begin != 0 or step_end >= 0:
+        raise NotImplementedError("segmented walks and fused statistics are not implemented for "
+                                  "categorical_table networks")
+    n_out_cols = int(plan.out_cols.numel()) if plan.out_nodes else 0
+    want_lp = plan.mode != MODE_SAMPLE
+    pcs = _pc_state()
+    if pcs["on"]:
+        pcs.setdefault("seen", []).append(plan)
+        lp = torch.zeros(b, n, device=pk.device) if want_lp else torch.empty(0, device=pk.device)
+        return lp, torch.zeros(b, n, n_out_cols, device=pk.device)
+    _check_table_support(pk, plan, fixed)
+    if run_if is None:
+        LAST_LAUNCH.update(pk=pk, plan=plan, fixed=fixed, b=b, n=n, fixed_per_particle=fixed_per_particle,
+                           noise=noise, state=None, seed=seed, offset=offset, plan_jit=0, precomputed=False,
+                           q_base=q_base)
+    args = (plan.steps, plan.in_cols, pk.params, fixed, noise, plan.table_out_cols, b, n, plan.n_slots,
+            plan.fixed_ld, fixed_per_particle, noise_b, len(plan.noise_nodes), pk.dmax, n_out_cols, plan.mode,
+            q_base, seed, offset, want_lp)
+    if run_if is None and out_x is None:
+        lp, x = ops.table_walk(*args)
+    else:
+        lp, x = ops.table_walk_ex(*args, run_if=run_if,
+                                  out_x=None if out_x is None else out_x.view(b * n, n_out_cols))
+    if want_lp:
+        lp = lp.view(b, n)
+    if n_out_cols:
+        x = x.view(b, n, n_out_cols)
+    return lp, x
+
+
 def _stats_request(kwargs, xs: torch.Tensor) -> Optional[dict]:
     """The caller's fused posterior-summary request (``_stats``: a dict with "eps", filled with
     "mean" / "std" / "ess"; VBN.infer_relative) as normalize_weights_ex's ``stats`` argument, or
@@ -547,7 +619,7 @@ class MonteCarloMarginalization(_EngineBase):
         stats = kwargs.get("_stats")
         d = int(plan.out_cols.numel())
         part = None
-        if stats is not None and n % 64 == 0 and 1 <= d <= 15:
+        if stats is not None and n % 64 == 0 and 1 <= d <= 15 and not plan.tabular:
             # VBN._posterior_stats fused into the walk's epilogue (vbn_walk_args.stats_part)
             rows, stride = ops.stats_part_rows(b_eff, n, d)
             part = torch.empty(rows, stride, device=dev, dtype=torch.float64)
@@ -739,6 +811,7 @@ class RaoBlackwellizedMarginalization(_EngineBase):
         return self._fallback.infer_posterior(vbn, query, **kw)
 
     def infer_posterior(self, vbn, query, **kwargs):
+        _no_tables(vbn, "rao_blackwellized_marginalization")
         self._last_fallback = False
         self._last_reason = None
         n = max(1, int(kwargs.get("n_samples", self.n_samples)))
@@ -783,6 +856,58 @@ class RaoBlackwellizedMarginalization(_EngineBase):
         return pdf, support.view(1, -1, 1).expand(b, -1, 1)
 
 
+@register_inference("categorical_exact")
+class CategoricalExact:
+    """categorical_exact.py:13-128 on the GPU: the exact posterior row of a categorical_table
+    target whose parents are all observed (a PARAMS walk at S = 1: one row gather per query),
+    the configured fallback engine for every other query."""
+
+    def __init__(self, fallback: Optional[str] = "likelihood_weighting", **kwargs):
+        self.fallback = str(fallback).strip().lower() if fallback is not None else "none"
+        self._fallback = None
+        self._last_fallback = False
+        self.q_base = int(kwargs.get("q_base", 0))
+        if self.fallback != "none":
+            from .registry import INFERENCE_REGISTRY
+            if self.fallback not in INFERENCE_REGISTRY:
+                raise ValueError(
+                    f"Unknown fallback inference '{fallback}'. Available: {list(INFERENCE_REGISTRY.keys())}")
+            if self.fallback == "categorical_exact":
+                raise ValueError("fallback cannot be 'categorical_exact'")
+            self._fallback = INFERENCE_REGISTRY[self.fallback](**kwargs)
+
+    def _fallback_infer(self, vbn, query, **kwargs):
+        self._last_fallback = True
+        if self._fallback is None:
+            raise RuntimeError("categorical_exact cannot handle this query and has no fallback")
+        return self._fallback.infer_posterior(vbn, query, **kwargs)
+
+    def infer_posterior(self, vbn, query, **kwargs):
+        self._last_fallback = False
+        target, ev, do = _EngineBase._query(query)
+        b = infer_batch_size(ev, do)
+        dev = _device_of(vbn)
+        pk = packed_model(vbn, dev)
+        model = pk.model
+        vals = _fixed_values(query, dev, clamp=True)                                  # 95: clamp_obs
+        if target in vals:                                                            # 100-104
+            return (torch.ones(b, 1, device=dev, dtype=torch.float32),
+                    vals[target].unsqueeze(1).expand(b, 1, -1))
+        parents = model.parents[target]
+        rec = model.cpds[target]
+        if (not all(p in vals for p in parents) or rec.kind != "categorical_table"   # 106-125
+                or model.out_dim(target) != 1):
+            return self._fallback_infer(vbn, query, **kwargs)
+        nodes = set(parents) | {target}
+        plan = _plan(pk, ("cat-exact", target), latent=[], fixed=[x for x in model.topo if x in parents], logp=[],
+                     out_nodes=[target], params=[target], shared_roots=True, mode=MODE_SAMPLE,
+                     skip=[x for x in model.topo if x not in nodes])
+        fx = _fixed_buffer(plan, vals, b, dev)
+        _, probs = run_walk(pk, plan, fx, b, 1, seed=0, q_base=self.q_base)
+        support = rec.state["_sample_values"][0].to(device=dev, dtype=torch.float32)   # 81-82
+        return probs.view(b, -1), support.view(1, -1, 1).expand(b, -1, 1)
+
+
 @register_inference("resampled_importance_sampling")
 class ResampledImportanceSampling(_EngineBase):
     """resampled_importance_sampling.py:13-105 on the GPU (segmented walk + resampling)."""
@@ -797,6 +922,7 @@ class ResampledImportanceSampling(_EngineBase):
         self._last_resampled = False
 
     def infer_posterior(self, vbn, query, **kwargs):
+        _no_tables(vbn, "resampled_importance_sampling")
         n = int(kwargs.get("n_samples", self.n_samples))
         thr_in = float(kwargs.get("ess_threshold", self.ess_threshold))
         resample = bool(kwargs.get("resample", self.resample))
@@ -938,6 +1064,7 @@ class GibbsSampler(_EngineBase):
         target, ev, do = self._query(query)
         if not target:
             raise ValueError("Gibbs sampling needs a query target")
+        _no_tables(vbn, "gibbs sampling")
         b = infer_batch_size(ev, do)
         dev = _device_of(vbn)
         pk = packed_model(vbn, dev)

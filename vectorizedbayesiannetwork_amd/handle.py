@@ -9,8 +9,8 @@ the reference's formats (``cpd_handle.py:348-404``):
   (walk role PARAMS);
 * ``mixture_params``  -- mdn: ``weights`` = softmax(logits) [B, 1, K], ``loc`` / ``scale``
   [B, 1, K, D] (PARAMS);
-* ``categorical_probs`` -- softmax_nn: ``probs`` [B, 1, D, C], ``k``, ``support``
-  (``_sample_values``) (PARAMS);
+* ``categorical_probs`` -- softmax_nn, categorical_table: ``probs`` [B, 1, D, C], ``k``,
+  ``support`` (``_sample_values``) (PARAMS);
 * ``empirical_samples`` -- kde: ``n_samples`` GPU draws with their mean / std.
 
 As in the reference, tensors in the returned dicts go through ``to_serializable`` (nested
@@ -29,7 +29,7 @@ from .model import CPDRecord
 __all__ = ["CPDHandle", "to_serializable"]
 
 _CLASS_NAME = {"gaussian_nn": "GaussianNNCPD", "linear_gaussian": "LinearGaussianCPD", "mdn": "MDNCPD",
-               "kde": "KDECPD", "softmax_nn": "SoftmaxNNCPD"}
+               "kde": "KDECPD", "softmax_nn": "SoftmaxNNCPD", "categorical_table": "CategoricalTableCPD"}
 
 
 def to_serializable(obj, *, max_tensor_elems: int = 2048):
@@ -211,7 +211,10 @@ class CPDHandle:
             return {"format": "mixture_params", "weights": prm[..., :k],
                     "loc": prm[..., k:k + k * D].reshape(b, s, k, D),
                     "scale": prm[..., k + k * D:].reshape(b, s, k, D)}
-        c = int(self._rec.hp("n_classes"))
+        if kind == "categorical_table":          # n_classes = 0 means "as fitted": the table's width
+            c = int(self._rec.state["_counts"].shape[-1])
+        else:
+            c = int(self._rec.hp("n_classes"))
         return {"format": "categorical_probs", "probs": prm.reshape(b, s, D, c), "k": c,
                 "support": self._rec.state["_sample_values"].to(self._vbn.device)}
 

@@ -10,7 +10,11 @@ The accelerated path never imports the reference. It consumes either
   CPD's ``state_dict()`` / ``get_init_kwargs()`` / ``get_extra_state()``
   (reference ``core/base.py:66-81``); or
 * :func:`random_init_model`, which builds random-init weights of the reference
-  architectures (the bench's synthetic models).
+  architectures (the bench's synthetic models); or
+* :func:`random_table_model`, seeded random count tables of ``categorical_table`` CPDs.
+
+``categorical_table`` networks run on a walk of their own (``csrc/vbn_table_walk.hip``), so a
+model is either all ``categorical_table`` or holds none: mixed networks are refused at load.
 """
 from __future__ import annotations
 
@@ -30,12 +34,13 @@ __all__ = [
     "model_from_vbn",
     "record_from_cpd",
     "random_init_model",
+    "random_table_model",
     "checkpoint_from_model",
     "KIND_DEFAULTS",
 ]
 
 # Registry keys of the reference CPDs on the hot path (reference core/registry.py + cpds/*).
-CPD_KINDS = ("gaussian_nn", "linear_gaussian", "mdn", "kde", "softmax_nn")
+CPD_KINDS = ("gaussian_nn", "linear_gaussian", "mdn", "kde", "softmax_nn", "categorical_table")
 
 _CLASS_TO_KIND = {
     "GaussianNNCPD": "gaussian_nn",
@@ -43,10 +48,11 @@ _CLASS_TO_KIND = {
     "MDNCPD": "mdn",
     "KDECPD": "kde",
     "SoftmaxNNCPD": "softmax_nn",
+    "CategoricalTableCPD": "categorical_table",
 }
 
 # Constructor defaults of the reference classes (gaussian_nn.py:41-50, linear_gaussian.py:14-22,
-# mdn.py:41-51, kde.py:17-27, softmax_nn.py:52-71).  Values that a checkpoint carries in
+# mdn.py:41-51, kde.py:17-27, softmax_nn.py:52-71, categorical_table.py:27-38).  Values that a checkpoint carries in
 # ``init_kwargs`` override these.
 KIND_DEFAULTS: Dict[str, Dict[str, Any]] = {
     "gaussian_nn": dict(hidden_dims=(32, 32), activation="relu", min_scale=1e-3),
@@ -57,6 +63,8 @@ KIND_DEFAULTS: Dict[str, Dict[str, Any]] = {
                        min_bin_width=1e-12, binning="uniform", within_bin="uniform",
                        within_bin_scale=0.25, within_bin_clip=False,
                        mode_when_not_discrete="binned"),
+    "categorical_table": dict(n_classes=0, parent_n_classes=None, alpha=1.0, alpha_mode="per_class",
+                              prior="uniform"),
 }
 
 # The packaged YAML defaults the reference's ``defaults.cpd(kind)`` returns
@@ -68,6 +76,7 @@ YAML_DEFAULTS: Dict[str, Dict[str, Any]] = {
     "kde": dict(bandwidth=0.5, parent_bandwidth=0.5, max_points=4096, min_scale=1e-4),
     "softmax_nn": dict(n_classes=8, hidden_dims=(32, 32), activation="relu",
                        min_bin_width=1e-12, binning="quantile", within_bin="triangular"),
+    "categorical_table": dict(n_classes=0, alpha=1.0, alpha_mode="total_mass", prior="global"),
 }
 
 
@@ -156,8 +165,94 @@ def _state_to_cpu(state: Mapping[str, Any]) -> Dict[str, torch.Tensor]:
 def _extra_to_cpu(extra: Any) -> Optional[Dict[str, Any]]:
     if not isinstance(extra, Mapping):
         return None
-    return {k: (v.detach().to("cpu") if isinstance(v, torch.Tensor) else v)
-            for k, v in extra.items()}
+    def cpu(v):
+        if isinstance(v, torch.Tensor):
+            return v.detach().to("cpu")
+        if isinstance(v, (list, tuple)):          # categorical_table: parent_values, a list of tensors
+            return [cpu(x) for x in v]
+        return v
+    return {k: cpu(v) for k, v in extra.items()}
+
+
+_OFF_PATH = "is not on the accelerated path"
+
+
+def _check_table_record(node: str, rec: "CPDRecord") -> None:
+    """A ``categorical_table`` record the table walk can run (csrc/vbn_table_walk.hip): fitted
+    state of consistent shapes, sorted valid class values in front of the masked ones, parent
+    supports and strides for every parent column."""
+    st = rec.state
+    for key in ("_counts", "_class_values", "_class_mask"):
+        if key not in st:
+            raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: its checkpoint has no {key}")
+    if "_stats_ready" in st and not bool(st["_stats_ready"]):
+        raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: it is not fitted (_stats_ready is False)")
+    counts, cv, mask = st["_counts"], st["_class_values"], st["_class_mask"].bool()
+    d = int(rec.output_dim)
+    if counts.dim() != 3 or cv.dim() != 2 or counts.shape[0] != d or tuple(cv.shape) != (d, counts.shape[2]) \
+            or mask.shape != cv.shape or counts.shape[2] < 1:
+        raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: _counts {tuple(counts.shape)}, _class_values "
+                         f"{tuple(cv.shape)} and _class_mask {tuple(mask.shape)} do not fit {d} output dims")
+    for k in range(d):
+        nv = int(mask[k].sum())
+        vals = cv[k][:nv]
+        if nv < 1 or not bool(mask[k][:nv].all()) or (nv > 1 and not bool((vals[1:] > vals[:-1]).all())):
+            raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: dim {k} needs its valid class values "
+                             "sorted in front of the masked ones")
+    extra = rec.extra or {}
+    n_in = int(rec.input_dim)
+    pv, cards, strides = extra.get("parent_values"), extra.get("parent_cards"), extra.get("parent_strides")
+    if n_in > 0:
+        if pv is None or strides is None or cards is None or not (len(pv) == len(cards) == len(strides) == n_in):
+            raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: no parent support / strides for its "
+                             f"{n_in} parent columns")
+        if any(int(c) != int(v.numel()) or int(c) < 1 for c, v in zip(cards, pv)):
+            raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: parent_cards do not match parent_values")
+        span = sum((int(c) - 1) * int(s) for c, s in zip(cards, strides))      # the largest configuration index
+        if min(int(s) for s in strides) < 1 or span >= int(counts.shape[1]):
+            raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: parent strides reach past its "
+                             f"{int(counts.shape[1])} parent configurations")
+    elif int(counts.shape[1]) != 1:
+        raise ValueError(f"categorical_table node '{node}' {_OFF_PATH}: a root table with "
+                         f"{int(counts.shape[1])} parent configurations")
+
+
+def _check_table_model(topo: Sequence[str], parents: Mapping[str, Sequence[str]],
+                       cpds: Mapping[str, "CPDRecord"]) -> None:
+    """Refuse what the table walk cannot run: a ``categorical_table`` next to any other kind
+    (mixed networks are out of scope), an unfitted or inconsistent record, and a child whose
+    support of a parent column is not that column's set of valid class values -- with equal
+    sets a sampled parent can never miss the child's support."""
+    kinds = {cpds[n].kind for n in topo}
+    if "categorical_table" not in kinds:
+        return
+    if len(kinds) > 1:
+        other = sorted(kinds - {"categorical_table"})
+        raise ValueError(f"a model that mixes categorical_table with {other} {_OFF_PATH}: the table walk runs "
+                         "networks whose every CPD is a categorical_table (mixed networks are out of scope)")
+    for n in topo:
+        _check_table_record(n, cpds[n])
+    for n in topo:
+        rec = cpds[n]
+        pv = (rec.extra or {}).get("parent_values") or []
+        col = 0
+        for p in parents[n]:
+            prec = cpds[p]
+            pm = prec.state["_class_mask"].bool()
+            for k in range(int(prec.output_dim)):
+                if col >= len(pv):
+                    raise ValueError(f"categorical_table node '{n}' {_OFF_PATH}: it has {len(pv)} parent columns, "
+                                     f"its parents are wider")
+                want = prec.state["_class_values"][k][pm[k]].to(torch.float32)
+                have = pv[col].to(torch.float32).reshape(-1)
+                if have.shape != want.shape or not bool((have == want).all()):
+                    raise ValueError(f"categorical_table node '{n}' {_OFF_PATH}: its support of parent '{p}' "
+                                     f"(column {col}: {have.tolist()}) is not the parent's class values "
+                                     f"{want.tolist()}")
+                col += 1
+        if col != int(rec.input_dim):
+            raise ValueError(f"categorical_table node '{n}' {_OFF_PATH}: input_dim {rec.input_dim} != parents "
+                             f"width {col}")
 
 
 def model_from_checkpoint(ckpt: Mapping[str, Any] | str) -> BNModel:
@@ -186,6 +281,7 @@ def model_from_checkpoint(ckpt: Mapping[str, Any] | str) -> BNModel:
             extra=_extra_to_cpu(extra),
         )
     parents = {n: list(p) for n, p in dag["parents"].items()}
+    _check_table_model(list(dag["topological_order"]), parents, cpds)
     return BNModel(
         nodes=list(dag["nodes"]),
         edges=[tuple(e) for e in dag["edges"]],
@@ -213,6 +309,11 @@ def checkpoint_from_model(model: BNModel, *, seed: Optional[int] = None, device:
         extra_state = None
         if rec.kind == "kde":
             extra_state = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in (rec.extra or {}).items()}
+        elif rec.kind == "categorical_table":
+            # get_extra_state (categorical_table.py:77-82): parent_values is a list of tensors
+            extra_state = {k: ([x.clone() for x in v] if k == "parent_values" and v is not None
+                               else (list(v) if isinstance(v, (list, tuple)) else v))
+                           for k, v in (rec.extra or {}).items()}
         sd = {k: v.clone() for k, v in rec.state.items()}
         sd["_extra_state"] = extra_state
         nodes_state[node] = {
@@ -303,6 +404,7 @@ def model_from_vbn(vbn: Any) -> BNModel:
         parents={n: list(dag.parents(n)) for n in dag.nodes()},
         cpds={n: record_from_cpd(vbn.nodes[n]) for n in topo},
     )
+    _check_table_model(model.topo, model.parents, model.cpds)
     try:
         vbn._vbn_amd_model = (key, model)
     except AttributeError:
@@ -437,3 +539,49 @@ def random_init_model(g: nx.DiGraph, kinds: Mapping[str, str], data: Mapping[str
         cpds[node] = CPDRecord(kind=kind, input_dim=d_in, output_dim=d_out, hparams=hp,
                                state=state, extra=extra)
     return BNModel(nodes=list(g.nodes), edges=list(g.edges), topo=topo, parents=parents, cpds=cpds)
+
+
+def random_table_model(g: nx.DiGraph, n_classes, seed: int = 0, *, class_values: Optional[Mapping[str, Sequence[float]]] = None,
+                       masked: Optional[Mapping[str, int]] = None, concentration: float = 1.0) -> BNModel:
+    """An all-``categorical_table`` model over the DAG ``g`` with seeded random count tables
+    (no reference involved): one-dimensional nodes, ``n_classes`` an int or a per-node mapping,
+    class values 0..C-1 unless ``class_values[node]`` gives other (sorted) ones, ``masked[node]``
+    trailing classes masked out as a fit with ``n_classes`` above the classes seen leaves them.
+    Counts are Gamma(``concentration``) draws + 0.05, so every valid class has mass."""
+    gen = torch.Generator().manual_seed(seed)
+    topo = list(nx.topological_sort(g))
+    parents = {n: list(g.predecessors(n)) for n in g.nodes}
+    card = {n: int(n_classes[n]) if isinstance(n_classes, Mapping) else int(n_classes) for n in topo}
+    cpds: Dict[str, CPDRecord] = {}
+    valid: Dict[str, torch.Tensor] = {}
+    for node in topo:
+        c = card[node]
+        nm = int((masked or {}).get(node, 0))
+        if c < 1 or not 0 <= nm < c:
+            raise ValueError(f"node {node}: {c} classes with {nm} masked")
+        cv = torch.zeros(1, c)
+        vals = torch.tensor(list((class_values or {}).get(node, range(c - nm))), dtype=torch.float32)
+        if vals.numel() != c - nm or (vals.numel() > 1 and not bool((vals[1:] > vals[:-1]).all())):
+            raise ValueError(f"node {node}: needs {c - nm} sorted class values")
+        cv[0, :c - nm] = vals
+        mask = torch.zeros(1, c, dtype=torch.bool)
+        mask[0, :c - nm] = True
+        valid[node] = vals
+        pv = [valid[p].clone() for p in parents[node]]
+        cards = [int(v.numel()) for v in pv]
+        strides, stride = [], 1
+        for k in reversed(cards):
+            strides.append(stride)
+            stride *= k
+        strides = list(reversed(strides))
+        shape = torch.empty(1, stride, c).fill_(float(concentration))
+        counts = torch._standard_gamma(shape, generator=gen) + 0.05
+        counts = counts.masked_fill(~mask.unsqueeze(1), 0.0)
+        state = {"_class_values": cv, "_sample_values": cv.clone(), "_class_mask": mask, "_counts": counts,
+                 "_stats_ready": torch.tensor(True)}
+        extra = {"parent_values": pv, "parent_cards": cards, "parent_strides": strides}
+        cpds[node] = CPDRecord(kind="categorical_table", input_dim=len(pv), output_dim=1,
+                               hparams=dict(YAML_DEFAULTS["categorical_table"], n_classes=c), state=state, extra=extra)
+    model = BNModel(nodes=list(g.nodes), edges=list(g.edges), topo=topo, parents=parents, cpds=cpds)
+    _check_table_model(model.topo, model.parents, model.cpds)
+    return model

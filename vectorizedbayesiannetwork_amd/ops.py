@@ -2,6 +2,7 @@
 
 * ``vbn_hip::walk``               -> ``vbn_hip_walk``             (particle pass)
 * ``vbn_hip::walk_segment``       -> ``vbn_hip_walk``             (one segment of a split pass)
+* ``vbn_hip::table_walk``         -> ``vbn_hip_table_walk``       (particle pass of an all-categorical_table plan)
 * ``vbn_hip::normalize_weights``  -> ``vbn_hip_normalize_weights`` (softmax over S + ESS)
 * ``vbn_hip::rb_epilogue``        -> ``vbn_hip_rb_epilogue``       (Rao-Blackwellized target)
 * ``vbn_hip::resample``           -> ``vbn_hip_resample``          (multinomial particle resampling)
@@ -23,7 +24,7 @@ from torch import Tensor
 from . import _lib
 from .plan import MODE_GIBBS, MODE_MCM, S_WBLK_LEN, STEP_INTS
 
-__all__ = ["walk", "walk_segment", "normalize_weights", "rb_epilogue", "resample", "posterior_stats"]
+__all__ = ["walk", "walk_segment", "table_walk", "normalize_weights", "rb_epilogue", "resample", "posterior_stats"]
 
 
 def _ptr(t: Optional[Tensor]) -> Optional[int]:
@@ -102,6 +103,110 @@ def walk_segment(steps: Tensor, in_cols: Tensor, params: Tensor, fixed: Tensor, 
                         max_out, fixed_ld, fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode,
                         q_base, seed, offset, want_lp, kind_mask, state, state_flags, step_begin, step_end,
                         wbuf)
+
+
+@torch.library.custom_op("vbn_hip::table_walk", mutates_args=())
+def table_walk(steps: Tensor, in_cols: Tensor, params: Tensor, fixed: Tensor, noise: Optional[Tensor],
+               out_cols: Tensor, n_queries: int, n_samples: int, n_slots: int, fixed_ld: int,
+               fixed_per_particle: bool, noise_b: int, n_noise: int, dmax: int, n_out_cols: int, mode: int,
+               q_base: int, seed: int, offset: int, want_lp: bool) -> Tuple[Tensor, Tensor]:
+    """One particle walk of a plan whose every step is a categorical_table (plan.QueryPlan.tabular;
+    csrc/vbn_table_walk.hip).  ``params``: the model's whole table blob; ``out_cols``: the plan's
+    ``table_out_cols`` (slots ++ class-value offsets); the samples are class values."""
+    return table_walk_ex(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
+                         fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp)
+
+
+@table_walk.register_fake
+def _table_walk_fake(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
+                     fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp):
+    total = n_queries * n_samples
+    return params.new_empty(total if want_lp else 0), params.new_empty((total, n_out_cols) if n_out_cols > 0 else (0,))
+
+
+def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
+                fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp,
+                run_if=None, out_x=None):
+    """Checked arguments of a table walk: (VbnWalkArgs, lp, x)."""
+    device = params.device
+    if device.type != "cuda":
+        raise RuntimeError(f"vbn_hip::table_walk runs on the GPU only (no CPU fallback); params are on {device}")
+    for name, t, dt in (("steps", steps, torch.int32), ("in_cols", in_cols, torch.int32),
+                        ("out_cols", out_cols, torch.int32), ("params", params, torch.float32),
+                        ("fixed", fixed, torch.float32)):
+        _check_dev(name, t, dt, device)
+    if steps.dim() != 2 or steps.shape[1] != STEP_INTS:
+        raise ValueError("vbn_hip::table_walk: steps must be [n_steps, 32]")
+    if mode not in (MODE_MCM, 1, 2):
+        raise ValueError("vbn_hip::table_walk: mode must be MCM, WEIGHTED or SAMPLE")
+    if params.numel() % 256 or params.numel() == 0:
+        raise ValueError("vbn_hip::table_walk: params must be a table blob of a multiple of 256 floats")
+    if n_out_cols > 0 and out_cols.numel() < 2 * n_out_cols:
+        raise ValueError(f"vbn_hip::table_walk: out_cols needs {n_out_cols} slots ++ {n_out_cols} class-value offsets")
+    total = n_queries * n_samples
+    rows = total if fixed_per_particle else n_queries
+    if fixed.numel() < rows * fixed_ld:
+        raise ValueError(f"vbn_hip::table_walk: fixed buffer has {fixed.numel()} values, needs {rows}x{fixed_ld}")
+    if noise is not None:
+        _check_dev("noise", noise, torch.float32, device)
+        need = n_noise * 2 * noise_b * n_samples * dmax
+        if noise.numel() < need or noise_b not in (1, n_queries):
+            raise ValueError(f"vbn_hip::table_walk: noise has {noise.numel()} values, needs {need}")
+    lp = torch.empty(total if want_lp else 0, device=device, dtype=torch.float32)
+    if out_x is None:
+        x = torch.empty((total, n_out_cols) if n_out_cols > 0 else (0,), device=device, dtype=torch.float32)
+    else:
+        _check_dev("out_x", out_x, torch.float32, device)
+        if n_out_cols <= 0 or out_x.numel() != total * n_out_cols:
+            raise ValueError(f"vbn_hip::table_walk: out_x must be a contiguous [{total}, {n_out_cols}] float32 tensor")
+        x = out_x
+    if run_if is not None:
+        _check_dev("run_if", run_if, torch.int32, device)
+    a = _lib.VbnWalkArgs()
+    a.steps = _ptr(steps)
+    a.in_cols = in_cols.data_ptr()
+    a.params = _ptr(params)
+    a.fixed = _ptr(fixed)
+    a.noise = _ptr(noise)
+    a.out_cols = _ptr(out_cols)
+    a.out_lp = _ptr(lp)
+    a.out_x = _ptr(x)
+    a.n_queries = n_queries
+    a.n_samples = n_samples
+    a.n_steps = int(steps.shape[0])
+    a.n_slots = n_slots
+    a.max_out = 0
+    a.fixed_ld = fixed_ld
+    a.fixed_per_particle = int(fixed_per_particle)
+    a.noise_b = noise_b
+    a.n_noise = n_noise
+    a.dmax = dmax
+    a.n_out_cols = n_out_cols
+    a.mode = mode
+    a.kind_mask = 1024
+    a.q_base = q_base
+    a.seed = seed & ((1 << 64) - 1)
+    a.offset = offset & ((1 << 64) - 1)
+    a.wbuf_floats = int(params.numel())
+    a.run_if = _ptr(run_if)
+    return a, lp, x
+
+
+def table_walk_ex(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
+                  fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp, *,
+                  run_if=None, out_x=None):
+    """:func:`table_walk` as a plain launch, plus ``run_if`` / ``out_x`` as in :func:`walk_ex`."""
+    a, lp, x = _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
+                           fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset,
+                           want_lp, run_if, out_x)
+    lib = _lib.load()
+    device = params.device
+    with torch.cuda.device(device):
+        LAST_WALK["table_staged"] = lib.vbn_hip_table_walk_staged(ctypes.byref(a)) == 1
+        _lib.check(lib.vbn_hip_table_walk(ctypes.byref(a), ctypes.c_void_p(_stream_handle(device))),
+                   "vbn_hip_table_walk")
+    LAST_WALK["specialised"] = False
+    return lp, x
 
 
 @walk_segment.register_fake
@@ -770,6 +875,9 @@ def _query_walk(plan, params, fixed, n_samples, seed, offset, q_base, noise, pla
     secs = _unpack(plan, device)
     if secs[0] is None:
         raise ValueError("vbn_hip: plan has no walk section")
+    if int(secs[0][3][8]) & 1024:
+        raise NotImplementedError("vbn_hip: the query-level ops are not implemented for categorical_table plans "
+                                  "(use the engines, which run them on vbn_hip::table_walk)")
     b = int(fixed.shape[0])
     if fixed.dim() != 2 or fixed.shape[1] < secs[0][3][6]:
         raise ValueError(f"vbn_hip: fixed must be [B, {secs[0][3][6]}] (plan fixed-buffer columns)")

@@ -29,7 +29,8 @@ import torch.nn.functional as F
 from .model import BNModel, CPDRecord
 
 # ---- must match include/vbn_hip.h -------------------------------------------------------
-KIND_ID = {"gaussian_nn": 0, "linear_gaussian": 1, "mdn": 2, "kde": 3, "softmax_nn": 4}
+KIND_ID = {"gaussian_nn": 0, "linear_gaussian": 1, "mdn": 2, "kde": 3, "softmax_nn": 4, "categorical_table": 5}
+KIND_MASK_TABLE = 1024    # kind_mask of a plan whose walked steps are all categorical_table (bit 5 = non-relu)
 ROLE_SKIP, ROLE_LATENT, ROLE_FIXED, ROLE_PARAMS, ROLE_SELECT, ROLE_COLLECT = 0, 1, 2, 3, 4, 5
 F_LOGP, F_ROOT, F_SHARED, F_STANDARDIZE, F_CLIP, F_F32L2, F_KDE_VALU = 1, 2, 4, 8, 16, 32, 64
 F_KEEP, F_LPRESET, F_BM_FIRST, F_BM_SECOND, F_MLP_GENERIC = 128, 256, 512, 1024, 2048
@@ -412,6 +413,60 @@ def _pack_mlp(blob: _Blob, rec: CPDRecord, standardize: bool) -> Dict[str, int]:
     return offs
 
 
+def _pack_table(blob: _Blob, rec: CPDRecord) -> Dict[str, int]:
+    """Rows of a categorical_table node for csrc/vbn_table_walk.hip, computed with the reference's
+    own float32 torch ops for every parent configuration at once (categorical_table.py:359-377:
+    probs = counts / sum.clamp_min(1e-12), logits = log(probs.clamp_min(1e-12)); masked classes
+    keep the ~1e-12 mass that arithmetic gives them):
+
+    * ``pts``: log_softmax(logits) (log_prob, :413) -- the reference's per-call value, bit for bit
+      wherever the host's float32 log is correctly rounded (see below);
+    * ``w1``: the inverse-CDF row of softmax(logits) (Categorical(logits=...), :389), accumulated
+      in float64 and rounded to float32 once;
+    * ``w2``: softmax(logits), the probability row of categorical_exact.py:71 (role PARAMS);
+    * ``w3`` class values [D][Cp], ``b3`` valid classes per dim, ``tail`` (stride, cardinality)
+      per parent column (int32 bits).
+
+    Rows are [D][P][Cp] with Cp = C rounded up to 4 floats (16-byte loads); the CDF padding
+    repeats the row total, the other paddings are 0."""
+    st = rec.state
+    counts = st["_counts"].to(torch.float32)                       # [D, P, C]
+    d, p, c = (int(x) for x in counts.shape)
+    cp = -(-c // 4) * 4
+    probs = counts / counts.sum(dim=-1, keepdim=True).clamp_min(1e-12)
+    # the float32 log as the correctly rounded value of the float64 log: torch's float32 log goes
+    # through the host's vector math library, whose last bit differs between CPU vendors (and from
+    # the correctly rounded value for ~0.1 % of arguments), so a table packed on one host would not
+    # reproduce log-probs recorded on another; every other op here is the reference's float32 op
+    logits = torch.log(probs.clamp_min(1e-12).double()).to(torch.float32)
+    logp = torch.log_softmax(logits, dim=-1)
+    # Categorical(logits=l) samples from softmax(l - logsumexp(l)) = softmax(l) up to rounding
+    # (torch/distributions/categorical.py); the fused float32 softmax is the same on every host
+    exact = torch.softmax(logits, dim=-1)
+    cdf = exact.double().cumsum(dim=-1).to(torch.float32)
+
+    def rows(t: torch.Tensor, pad_last: bool = False) -> np.ndarray:
+        out = np.zeros((d, p, cp), np.float32)
+        out[:, :, :c] = _np(t)
+        if pad_last:
+            out[:, :, c:] = out[:, :, c - 1:c]
+        return out
+
+    offs = {"pts": blob.add(rows(logp)), "w1": blob.add(rows(cdf, pad_last=True)), "w2": blob.add(rows(exact))}
+    cv = np.zeros((d, cp), np.float32)
+    cv[:, :c] = _np(st["_class_values"])
+    offs["w3"] = blob.add(cv)
+    nv = st["_class_mask"].bool().sum(dim=-1).to(torch.int32).numpy()
+    offs["b3"] = blob.add(np.ascontiguousarray(nv, np.int32).view(np.float32))
+    extra = rec.extra or {}
+    hdr = np.zeros((max(rec.input_dim, 1), 2), np.int32)
+    for j in range(rec.input_dim):
+        hdr[j] = (int(extra["parent_strides"][j]), int(extra["parent_cards"][j]))
+    offs["tail"] = blob.add(hdr.view(np.float32))
+    offs["_table"] = (c, p, cp)
+    return offs
+
+
 @dataclass
 class NodePack:
     kind: int
@@ -432,12 +487,17 @@ def _pack_node(blob: _Blob, rec: CPDRecord) -> NodePack:
     D = rec.output_dim
     root = rec.is_root
     flags = F_ROOT if root else 0
-    act = ACT_ID.get(str(rec.hp("activation") or "relu"), -1)
-    if act < 0:
-        raise ValueError(f"unknown activation {rec.hp('activation')}")
     st = rec.state
     offs: Dict[str, int] = {}
     k = n_out = aux0 = aux1 = 0
+    if kind == "categorical_table":
+        offs = _pack_table(blob, rec)
+        k, aux0, aux1 = offs.pop("_table")
+        return NodePack(kind=KIND_ID[kind], flags=flags, act=0, n_in=rec.input_dim, out_dim=D, k=k, n_out=0,
+                        aux0=aux0, aux1=aux1, offs=offs, scratch=0)
+    act = ACT_ID.get(str(rec.hp("activation") or "relu"), -1)
+    if act < 0:
+        raise ValueError(f"unknown activation {rec.hp('activation')}")
     if kind == "gaussian_nn":
         if root:
             loc = st["_loc"].view(1, 1, -1)
@@ -573,8 +633,13 @@ class PackedModel:
             if rec.input_dim != expect:
                 raise ValueError(f"node {node}: CPD input_dim {rec.input_dim} != parents width {expect}")
             self.nodes[node] = _pack_node(blob, rec)
-        host = torch.from_numpy(blob.finish())
-        self.params = host.to(self.device)
+        host = blob.finish()
+        # an all-categorical_table model walks on vbn_hip_table_walk, which stages the whole blob
+        # into LDS in 1-KiB chunks: its length is a multiple of the chunk
+        self.tabular = all(p.kind == KIND_ID["categorical_table"] for p in self.nodes.values())
+        if self.tabular and host.size % WBLK_CHUNK:
+            host = np.concatenate([host, np.zeros((-host.size) % WBLK_CHUNK, np.float32)])
+        self.params = torch.from_numpy(host).to(self.device)
         self.node_id = {n: i for i, n in enumerate(model.topo)}
         self.max_out = max([p.scratch for p in self.nodes.values()] + [1])
         self.has_kde = any(p.kind == KIND_ID["kde"] for p in self.nodes.values())
@@ -605,6 +670,12 @@ class QueryPlan:
     pc: Optional["QueryPlan"] = None
     pre: Optional["QueryPlan"] = None
     pre_q: Optional["QueryPlan"] = None
+    # every walked step is a categorical_table: the plan runs on vbn_hip_table_walk (kind_mask
+    # 1024, wbuf = the blob's length, out_cols = slots ++ class-value offsets), in the model's
+    # topological order (the log-weights add in the reference's order), without precompute plans
+    tabular: bool = False
+    table_out_cols: Optional[torch.Tensor] = None     # int32: out_cols ++ the columns' class-value offsets
+    table_check: Optional[List[Tuple[str, int, bool]]] = None   # (fixed node, its fixed column, clamped) to validate
 
 
 def barren_pruned(model: BNModel, keep: Sequence[str]) -> set:
@@ -723,6 +794,8 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
             return 2 * model.out_dim(n)                               # loc ++ scale
         if rec.kind == "softmax_nn":
             return model.out_dim(n) * int(rec.hp("n_classes"))        # class probabilities [D][C]
+        if rec.kind == "categorical_table":
+            return model.out_dim(n) * int(packed.nodes[n].k)          # class probabilities [D][C]
         if rec.kind == "mdn":
             return int(rec.hp("n_components")) * (1 + 2 * model.out_dim(n))  # weights, loc, scale
         raise ValueError(f"no parameter output for {rec.kind} node {n}")
@@ -848,6 +921,26 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
                 kind_mask |= 32
             if npk.flags & F_MLP_GENERIC:
                 kind_mask |= 512                 # csrc kind-set bit 9: the generic-MLP path
+    tabular = bool(getattr(packed, "tabular", False))
+    wbuf = int(steps[:, S_WBLK_LEN].max()) if len(order) else 0
+    if tabular:
+        kind_mask = KIND_MASK_TABLE
+        wbuf = int(packed.params.numel())
+        # the table walk keeps class indices in the slots: per output column, where its class
+        # values are in the blob (-1: a PARAMS column, the slot holds the probability itself)
+        # fixed nodes whose value the walk turns into a class index that something reads (a
+        # log-prob, a reading child, an output): the host checks them against the class set
+        # before the launch (engines.run_walk), as the reference's _map_values_to_indices does
+        read_by = {p for n in order if reads[n] for p in model.parents[n]}
+        table_check = [(n, fixed_col[n], n in clamp_s) for n in fixed_nodes
+                       if n in logp_s or n in read_by or n in set(out_nodes)]
+        cv_offs: List[int] = []
+        for n in out_nodes:
+            npk = packed.nodes[n]
+            if n in params_s:
+                cv_offs.extend([-1] * width(n))
+            else:
+                cv_offs.extend(npk.offs["w3"] + dd * npk.aux1 for dd in range(npk.out_dim))
     max_out = max([packed.nodes[n].scratch for n in order] + [1])
     if any(packed.nodes[n].kind == KIND_ID["kde"] for n in order):
         max_out = max(max_out, KDE_CHUNKS)
@@ -862,7 +955,8 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
         in_cols=t(in_cols), out_cols=t(out_cols), n_steps=len(order), n_slots=max(n_slots, 1),
         max_out=max_out, fixed_nodes=fixed_nodes, fixed_ld=max(c, 1), noise_nodes=noise_nodes,
         out_nodes=list(out_nodes), mode=mode, slot_of=slot_of, kind_mask=kind_mask, order=list(order),
-        wbuf=int(steps[:, S_WBLK_LEN].max()) if len(order) else 0)
+        wbuf=wbuf, tabular=tabular, table_out_cols=t(out_cols + cv_offs) if tabular else None,
+        table_check=table_check if tabular else None)
 
 
 def _pair_normals(steps: np.ndarray) -> None:
