@@ -101,8 +101,16 @@ enum vbn_mode {
  * length in floats), which the walk stages into LDS one step ahead (0 = the step runs no
  * MLP); the exact-f32 W2 copy (off_w2) deliberately stays outside the block and is read from
  * global memory on the rare exact path; [7] = (ABI v12) kde steps: the one-feature moment
- * table of pass 1 (plan.py kde_moment_table: header [u_lo, 1/delta, delta, n_cells] then
- * [n_cells][16 chunks][4 terms] f32), -1 = none; -1 on every other step.  KDE packs [1] (parent features) and
+ * table of pass 1 (plan.py kde_moment_table: header of 8 floats [u_lo, 1/delta, delta, n_cells,
+ * n_chunks, chunk points (int32 bits), 0, 0] then [n_cells][n_chunks + n_groups + 1][4 terms]
+ * f32: the chunks, their groups of 8, the whole point set), -1 = none; -1 on every other step.
+ * off_w1 on kde steps (an NN field otherwise): the two-feature moment table of pass 1 (plan.py
+ * kde_moment_table2: header of 16 floats -- per feature [u_lo, 1/delta, delta, n_cells (int32
+ * bits)], then rows per cell, floats per row, K (int32 bits), zeros -- then [n_cells0 *
+ * n_cells1][rows][48] f32, rows = the 16 chunks of the MFMA pass and, where that pass keeps
+ * half sums, the first half of each; a row = the 45 coefficients T[a,b], a + b < 9, in the
+ * order of csrc kde_mt2_row's nested Horner, padded to 16 bytes), -1 = none.
+ * KDE packs [1] (parent features) and
  * [2] (parent ++ target features) hold the bf16x3 slots of v_mfma_f32_16x16x32_bf16
  * ([block][quarter][16 points][8 bf16], plan.py _kde_pack_bf16); [3] = per-point f32 records,
  * [4] = the packed-VALU layout. */

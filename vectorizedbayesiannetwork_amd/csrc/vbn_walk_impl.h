@@ -44,6 +44,9 @@
 #define KDE_CHUNKS 16
 // kde steps: blob offset of the one-feature moment table (plan.kde_moment_table), -1 = none
 #define KDE_MT(st) ((st).reserved[7])
+// kde steps: blob offset of the two-feature moment table (plan.kde_moment_table2), -1 = none
+// (off_w1 is an NN field; the packer writes it on every kde step)
+#define KDE_MT2(st) ((st).off_w1)
 #define KDE_REC_TAIL 16  // weight-0 record rows after the last point (plan.py KDE_REC_TAIL)
 #define LOG_2PI_F 1.8378770664093453f
 
@@ -1711,6 +1714,76 @@ __device__ __forceinline__ int kde_index_moments(const float* __restrict__ T, fl
                   [&](const float4 r) { return fmaf(r.y, -1.f, fmaf(r.x, xb0, -0.f)); });
 }
 
+// Two-feature node with a 2-D moment table (plan.kde_moment_table2): pass 1 of kde_index_mfma
+// without its exps.  Around the cell centre u_g nearest u = 2 x', d = u - u_g, a chunk's sum is
+//   S_c(u) = sum_{a+b<K} d0^a d1^b T[g][c][a,b],
+//   T[g][c][a,b] = sum_{j in c} exp2(u_g.y'_j - |y'_j|^2) (ln2 y'_j0)^a (ln2 y'_j1)^b / (a! b!)
+// (float64 sums, host); the cell widths keep ln2 |d.y'| <= Z = 0.5, so the remainder after
+// total degree K - 1 = 8 is < 8.9e-9 of every weight.  A row is its K (K + 1) / 2 = 45
+// coefficients in the order of the nested Horner below (a from K - 1 down, inside it b from
+// K - 1 - a down), padded to KDE_MT2_ROW4 float4; per cell the 16 chunk rows of the MFMA pass
+// (kde_cb) and, where that pass keeps half sums (KDE_HALF_MIN), the 16 first-half rows
+// (kde_sub_blocks(cb32, 1)), so everything after pass 1 is kde_index_mfma's own code.
+// Factored form (shift 0).  Header: per feature [u_lo, 1 / delta, delta, n_cells], then rows
+// per cell, floats per row, K (int32 bits), zeros (KDE_MT2_HEAD floats).
+#define KDE_MT2_HEAD 16       // header floats (plan.KDE_MT2_HEADER)
+#define KDE_MT2_K 9           // plan.KDE_MT2_K
+#define KDE_MT2_ROW4 12       // float4 per row: 45 coefficients padded to 48 (plan.KDE_MT2_ROW)
+struct KdeMt2 {
+  const float4* cell;         // the lane's cell: [rows][KDE_MT2_ROW4]
+  float d0, d1;
+};
+
+__device__ __forceinline__ float kde_mt2_row(const float4* __restrict__ row, float d0, float d1) {
+  // the row is streamed: float4 i is loaded when the Horner reaches coefficient 4 i, so a few
+  // float4 are live at a time, not the row's 12
+  float4 v = row[0];
+  int i = 0;
+  auto next = [&]() {
+    const int k = i & 3;
+    if (i && !k) v = row[i >> 2];
+    ++i;
+    return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
+  };
+  float s = next();                                  // a = K - 1: the one coefficient b = 0
+#pragma unroll
+  for (int a = KDE_MT2_K - 2; a >= 0; --a) {
+    float p = next();                                // b = K - 1 - a
+#pragma unroll
+    for (int b = KDE_MT2_K - 2 - a; b >= 0; --b) p = fmaf(p, d1, next());
+    s = fmaf(s, d0, p);
+  }
+  return s;
+}
+
+__device__ __noinline__ float kde_mt2_row_call(const float4* __restrict__ row, float d0, float d1) {
+  return kde_mt2_row(row, d0, d1);
+}
+
+// The 16 chunk sums of the lane's cell -> scr[chunk][lane], their float64 total -> tot.  False
+// for the whole wave (nothing to rely on in scr) when some lane's u is off the grid or NaN.
+__device__ __forceinline__ bool kde_index_moments2(const float* __restrict__ T, float u0, float u1, const Lane& L,
+                                                   bool halves, double& tot, KdeMt2& m) {
+  const cfloat* H = CP(T);
+  const float g0 = rintf((u0 - H[0]) * H[1]), g1 = rintf((u1 - H[4]) * H[5]);   // NaN u: not in range
+  const int n0 = __float_as_int(H[3]), n1 = __float_as_int(H[7]);
+  const bool in = g0 >= 0.f && g0 < (float)n0 && g1 >= 0.f && g1 < (float)n1;
+  if (!__all(in)) return false;
+  m.d0 = u0 - fmaf(g0, H[2], H[0]);                  // the centres exactly as the host formed them
+  m.d1 = u1 - fmaf(g1, H[6], H[4]);
+  const int rows = halves ? 2 * KDE_CHUNKS : KDE_CHUNKS;
+  m.cell = reinterpret_cast<const float4*>(T + KDE_MT2_HEAD) + ((int)g0 * n1 + (int)g1) * (rows * KDE_MT2_ROW4);
+  double t = 0.0;
+#pragma unroll 1
+  for (int ch = 0; ch < KDE_CHUNKS; ++ch) {
+    const float cs = kde_mt2_row(m.cell + ch * KDE_MT2_ROW4, m.d0, m.d1);
+    L.scr[ch * WAVE + L.lane] = cs;
+    t += (double)cs;
+  }
+  tot = t;
+  return true;
+}
+
 // Latent non-root KDE node, parent dims 1..3: index ~ softmax_j log K_p (kde.py:172-178).
 // Pass 1 (MFMA): per-chunk weight sums -> scr[chunk][lane]; pass 2 (VALU replica): locate the
 // chunk holding u * total, scan it.  All-underflow particles (every weight 0) redo the sums on
@@ -1745,6 +1818,26 @@ __device__ __forceinline__ int kde_index_mfma(const vbn_walk_args& A, const vbn_
   // pass 1 also keeps each chunk's first-half sum (a private array, kde_sub_blocks), so the
   // scan covers the half holding the threshold: at most a quarter chunk instead of a half
   bool halves = false;
+  // a two-feature node with a moment table: pass 1's chunk sums from the table (factored form,
+  // sigma 0) when every lane is on its grid; the located chunk's half sum is then one more row.
+  // A wave whose total is not safely positive somewhere runs the MFMA pass and its rescue.
+  bool tab2 = false;
+  KdeMt2 mt2 = {nullptr, 0.f, 0.f};
+  if (nf == 2 && KDE_MT2(st) >= 0 && !(st.flags & (VBN_F_PRECOMP | VBN_F_PRE_OUT)) &&
+      __all(-negsq <= KDE_FFORM_MAX)) {
+#ifndef VBN_ABL_NOHALVES
+    const bool h2 = KDE_NSUB == 2 && (cb >> 1) >= KDE_HALF_MIN;   // the table's half rows are halves
+#else
+    const bool h2 = false;
+#endif
+    double t2 = 0.0;
+    if (kde_index_moments2(L.P + KDE_MT2(st), 2.f * xv[0], 2.f * xv[1], L, (cb >> 1) >= KDE_HALF_MIN, t2, mt2) &&
+        __all(t2 >= (double)kde_tiny(M))) {
+      tab2 = true;
+      halves = h2;
+      tot = t2;
+    }
+  }
 #ifndef VBN_ABL_NOHALVES
   float hs[KDE_CHUNKS * (KDE_NSUB - 1)];
 #endif
@@ -1766,7 +1859,7 @@ __device__ __forceinline__ int kde_index_mfma(const vbn_walk_args& A, const vbn_
       }
       shift = q[KDE_CHUNKS];
     }
-  } else
+  } else if (!tab2)
 #ifdef VBN_ABL_NOP1
   if (true) {
     for (int ch = 0; ch < KDE_CHUNKS; ++ch) { L.scr[ch * WAVE + lane] = 1.f; tot += 1.0; }
@@ -1839,7 +1932,8 @@ __device__ __forceinline__ int kde_index_mfma(const vbn_walk_args& A, const vbn_
     int klo = 0, khi = KDE_NSUB;
 #pragma unroll
     for (int k = 1; k < KDE_NSUB; ++k) {
-      const float pk = hs[ch * (KDE_NSUB - 1) + k - 1];
+      const float pk = tab2 ? kde_mt2_row_call(mt2.cell + (KDE_CHUNKS + ch) * KDE_MT2_ROW4, mt2.d0, mt2.d1)
+                            : hs[ch * (KDE_NSUB - 1) + k - 1];
       if (rd >= (double)pk) { klo = k; plo = pk; }
       else if (khi == KDE_NSUB) { khi = k; phi = pk; }
     }

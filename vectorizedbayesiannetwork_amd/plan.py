@@ -299,6 +299,128 @@ def kde_moment_table(y: np.ndarray) -> Optional[np.ndarray]:
     return np.concatenate([head, tab.astype(np.float32).reshape(-1)])
 
 
+# ---- moment tables of two-feature KDE nodes (csrc kde_index_moments2) ------------------------
+# The same series in two dimensions: around the cell centre (u_g0, u_g1) nearest u = 2 x', with
+# d = u - u_g,
+#   S_c(u) = sum_{a+b<K} d0^a d1^b T[g][c][a,b],
+#   T[g][c][a,b] = sum_{j in c} exp2(u_g.y'_j - |y'_j|^2) (ln2 y'_j0)^a (ln2 y'_j1)^b / (a! b!).
+# Each point's series is that of exp(z), z = ln2 (d0 y'_0 + d1 y'_1), cut after total degree
+# K - 1: its remainder is below |z|^K / K! e^|z|, and the cell widths delta_f = Z / (ln2 max|y'_f|)
+# keep |z| <= ln2 sum_f (delta_f / 2) max|y'_f| = Z.  (Z, K) = (0.5, 9): 0.5^9 / 9! e^0.5 = 8.9e-9
+# of every weight.  The chunks are the MFMA pass's own 16 (kde_cb), each with the sum of its first
+# half (kde_sub_blocks) where the MFMA pass keeps half sums, so everything after pass 1 -- chunk
+# location, half choice, scan -- is the MFMA path's code.
+KDE_MOMENTS2 = os.environ.get("VBN_KDE_MOMENTS2", "1") != "0"    # A/B: 0 = MFMA pass 1 for two-feature nodes
+KDE_MT2_Z = 0.5
+KDE_MT2_K = 9                    # terms of total degree < K: K (K + 1) / 2 = 45 coefficients per row
+KDE_MT2_COEFS = KDE_MT2_K * (KDE_MT2_K + 1) // 2
+KDE_MT2_ROW = (KDE_MT2_COEFS + 3) & ~3          # floats per row (16-byte padded)
+KDE_MT2_HEADER = 16              # floats: per feature u_lo, 1 / delta, delta, n_cells (int32 bits);
+                                 # rows per cell, floats per row, K (int32 bits); 0 ...
+KDE_MT2_MAX_BYTES = 32 << 20     # table size bound per node
+KDE_MT2_MARGINS = (2.0, 1.5, 1.0)    # scaled units covered beyond the data's extremes, per feature:
+                                 # the widest whose table fits KDE_MT2_MAX_BYTES
+KDE_HALF_MIN = 16                # csrc KDE_HALF_MIN: 32-point blocks per chunk for half sums
+
+
+def kde_moment2_order(k: int = KDE_MT2_K) -> List[Tuple[int, int]]:
+    """(a, b) of a row's coefficients in the order the kernel's nested Horner consumes them:
+    outer in d0 from a = K - 1 down, inner in d1 from b = K - 1 - a down."""
+    return [(a, b) for a in range(k - 1, -1, -1) for b in range(k - 1 - a, -1, -1)]
+
+
+def kde_moment2_geometry(m: int) -> Tuple[int, int, bool]:
+    """(points per chunk, points of a chunk's first half, half rows kept) of the MFMA pass
+    (csrc kde_cb, kde_sub_blocks with KDE_NSUB = 2, KDE_HALF_MIN)."""
+    cb = _kde_cb(m)
+    cb32 = cb // 2
+    return 16 * cb, 32 * ((cb32 // 2) & ~1), cb32 >= KDE_HALF_MIN
+
+
+def kde_moment2_cells(y: np.ndarray, z: float = KDE_MT2_Z, w: float = KDE_MT2_MARGINS[0]):
+    """Per-feature grids of two-feature points y' [m, 2] (float32, scaled): a list of (u_lo,
+    delta, 1 / delta, n_cells) with cell width Z / (ln2 max|y'_f|).  The particle range covered
+    is u = 2 x' in 2 [min y' - w, max y' + w], w scaled units (KDE_MT2_MARGINS): at most the
+    floor of kde_moment_cells' margin, not its max(span, 2) -- a 2-D grid three spans wide per
+    feature is 42-98 MiB for 10 of the 13 two-parent nodes of the M = 10,000 benchmark DAG (a
+    particle is a data point plus bandwidth noise, 0.85 scaled units for the default bandwidth;
+    DESIGN.md records the margin each node got and the share of waves that leave the grid).
+    A particle outside it sends its wave to the MFMA pass."""
+    y64 = np.asarray(y, np.float32).reshape(-1, 2).astype(np.float64)
+    out = []
+    for f in range(2):
+        c = y64[:, f]
+        lo, hi = 2.0 * (float(c.min()) - w), 2.0 * (float(c.max()) + w)
+        amax = float(np.abs(c).max())
+        delta32 = np.float32(hi - lo if amax == 0.0 else z / (math.log(2.0) * amax))
+        lo32 = np.float32(lo)
+        n = int(math.ceil((hi - lo) / float(delta32))) + 1
+        out.append((lo32, delta32, np.float32(1.0 / float(delta32)), n))
+    return out
+
+
+def kde_moment_table2(y: np.ndarray, z: float = KDE_MT2_Z, k: int = KDE_MT2_K) -> Optional[np.ndarray]:
+    """The moment table of two-feature KDE parent points y' [m, 2] (float32, scaled): header
+    (KDE_MT2_HEADER), then [n_cells0 * n_cells1][rows][row floats] float32 with rows = the 16
+    chunks of the MFMA pass, then (kde_moment2_geometry) the first half of each; a row holds its
+    K (K + 1) / 2 coefficients in kde_moment2_order, zero-padded to 16 bytes.  float64 sums
+    (a [cells x points] @ [points x coefficients] product per bounded point block), one
+    rounding.  None when the table would exceed KDE_MT2_MAX_BYTES or a cell's largest log2
+    weight leaves [KDE_MT_EXP_MIN, KDE_MT_EXP_MAX]."""
+    y32 = np.asarray(y, np.float32).reshape(-1, 2)
+    m = y32.shape[0]
+    per, half, halves = kde_moment2_geometry(m)
+    rows = KDE_CHUNKS * (2 if halves else 1)
+    order = kde_moment2_order(k)
+    rowf = (len(order) + 3) & ~3
+    for w in KDE_MT2_MARGINS:
+        (lo0, dl0, inv0, n0), (lo1, dl1, inv1, n1) = kde_moment2_cells(y32, z, w)
+        if n0 * n1 * rows * rowf * 4 <= KDE_MT2_MAX_BYTES:
+            break
+    else:
+        return None
+    y64 = y32.astype(np.float64)
+    sq = (y64 ** 2).sum(axis=1).astype(np.float32).astype(np.float64)     # |y'|^2 as the packs hold it
+    c0, c1 = kde_moment_centres(lo0, dl0, n0), kde_moment_centres(lo1, dl1, n1)
+    ly = math.log(2.0) * y64
+    pw = np.stack([ly[:, 0] ** a * ly[:, 1] ** b / (math.factorial(a) * math.factorial(b)) for a, b in order], axis=1)
+    tab = np.zeros((n0 * n1, rows, rowf), np.float64)
+    w_max = np.zeros(n0 * n1)
+    blk = max(256, (1 << 22) // (n0 * n1))                    # [cells x points] blocks of <= 32 MiB
+
+    def seg_sum(j0, j1):
+        acc = np.zeros((n0 * n1, len(order)))
+        for i0 in range(j0, j1, blk):
+            i1 = min(j1, i0 + blk)
+            # exp2(u_g.y' - |y'|^2), separable in the two features
+            e0 = np.exp2(c0[:, None] * y64[None, i0:i1, 0] - sq[None, i0:i1])
+            e1 = np.exp2(c1[:, None] * y64[None, i0:i1, 1])
+            wts = (e0[:, None, :] * e1[None, :, :]).reshape(n0 * n1, i1 - i0)
+            np.maximum(w_max, wts.max(axis=1), out=w_max)
+            acc += wts @ pw[i0:i1]
+        return acc
+
+    for c in range(KDE_CHUNKS):
+        j0, j1 = min(m, c * per), min(m, (c + 1) * per)
+        if j0 >= j1:
+            continue
+        jh = min(j1, j0 + half) if halves else j0
+        first = seg_sum(j0, jh) if jh > j0 else 0.0
+        tab[:, c, :len(order)] = first + (seg_sum(jh, j1) if j1 > jh else 0.0)
+        if halves:
+            tab[:, KDE_CHUNKS + c, :len(order)] = first
+    with np.errstate(divide="ignore"):
+        e_max = np.log2(w_max)
+    if not (e_max.max() <= KDE_MT_EXP_MAX and e_max.min() >= KDE_MT_EXP_MIN):
+        return None
+    head = np.zeros(KDE_MT2_HEADER, np.float32)
+    head[0:3] = [lo0, inv0, dl0]
+    head[4:7] = [lo1, inv1, dl1]
+    head[[3, 7]] = np.array([n0, n1], np.int32).view(np.float32)
+    head[8:11] = np.array([rows, rowf, k], np.int32).view(np.float32)
+    return np.concatenate([head, tab.astype(np.float32).reshape(-1)])
+
+
 def _np(t: torch.Tensor) -> np.ndarray:
     return t.detach().to("cpu", torch.float32).numpy()
 
@@ -563,6 +685,10 @@ def _pack_node(blob: _Blob, rec: CPDRecord) -> NodePack:
                 mt = kde_moment_table((_np(pts_p) * c_p).reshape(-1))
                 if mt is not None:
                     offs["kmt"] = blob.add(mt)
+            if dp == 2 and KDE_MOMENTS2:              # pass 1 from a 2-D moment table (kde_index_moments2)
+                mt = kde_moment_table2(_np(pts_p) * c_p)
+                if mt is not None:
+                    offs["kmt2"] = blob.add(mt)
         if dp + D <= 4:
             feats = np.concatenate(([_np(pts_p).reshape(m, -1) * c_p] if dp else [])
                                    + [_np(pts_y).reshape(m, -1) * c_y], axis=1)
@@ -899,6 +1025,8 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
         row[S_OFF_KR] = npk.offs.get("kr", -1)
         row[S_OFF_KV] = npk.offs.get("kv", -1)
         row[S_RES7] = npk.offs.get("kmt", -1)   # kde: moment table of a one-feature node
+        if npk.kind == KIND_ID["kde"]:          # kde: 2-D moment table of a two-feature node (off_w1
+            row[S_OFF_W1] = npk.offs.get("kmt2", -1)      # is an NN field: -1 = none on kde steps)
         if "wblk" in npk.offs and (n in latent_s or n in logp_s or n in params_s):
             row[S_WBLK_OFF] = npk.offs["wblk"]
             row[S_WBLK_LEN] = npk.offs["wblk_len"]
