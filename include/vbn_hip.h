@@ -90,9 +90,8 @@ int vbn_hip_table_walk(const vbn_walk_args* args, void* stream);
  * them from global memory, -(error code) for arguments it refuses. */
 int vbn_hip_table_walk_staged(const vbn_walk_args* args);
 
-/* The kind-set instantiation (walk_inst.hip / VBN_WALK_KIND_SETS: CPD kinds | 64 half-wave |
- * 128 lean | 256 half-wave without injected draws | 512 generic MLP) vbn_hip_walk would launch
- * for these arguments, or -(error code). */
+/* The kind-set instantiation (walk_inst.hip / VBN_WALK_KIND_SETS: CPD kinds and the VBN_KM_* bits
+ * of vbn_hip_types.h) vbn_hip_walk would launch for these arguments, or -(error code). */
 int vbn_hip_walk_kind_set(const vbn_walk_args* args);
 
 /* Plan-specialised walks.  A code object compiled at run time (hiprtc) from
@@ -113,7 +112,7 @@ int vbn_hip_module_unload(void* handle);
  * slots (n_slots rows) and n_waves x max(max_out, 1) scratch rows; the waves split each sweep's
  * node updates level by level (and a split level's steps phase by phase).  Same outputs as the
  * sequential sweep, bit for bit.  Only mode GIBBS launches are accepted for such a module; a
- * launch without injected draws may run a module compiled for its kind set | 256 (draw-free).
+ * launch without injected draws may run a module compiled for its kind set | VBN_KM_NOISELESS.
  * (Replaces the same reference call site as the Gibbs walk: GibbsSampler.sample,
  * vbn/sampling/gibbs.py:36-87.) */
 int vbn_hip_module_chain_waves(void* handle, int32_t n_waves);

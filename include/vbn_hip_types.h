@@ -57,7 +57,7 @@ enum vbn_role {
                                    exact f32 MFMA tiles through LDS; off_w2 points at the layer
                                    table [L, (in, out, off_w, off_b) x L] (int32 in the blob)   */
 #define VBN_F_HEAD_MFMA 4096    /* NN CPD head (8..32 outputs) on the split-f16 MFMA like layer 2:
-                                   reserved[2] = its fragments [hi 2][64][8 f16] ++ [lo ...]
+                                   off_kqy = its fragments [hi 2][64][8 f16] ++ [lo ...]
                                    (1024 floats), then the accumulator-init bias [2][16]      */
 #define VBN_F_PRECOMP 8192      /* per-sample quantities of a node whose parents are all shared
                                    root draws (MCM / LW / ancestral, Q5), computed once per sample
@@ -93,35 +93,57 @@ enum vbn_mode {
                              n_samples = 8 candidates; out_x = [B][n_collect][n_out_cols]    */
 };
 
-/* One node of the topological walk (32 x int32, filled by the host plan packer).
- * reserved[0] = split-f16 W2 fragments; [1..4] = KDE point packs (NN steps: [1] = the layer-1
- * operand bound zlim as float bits, [2] = the VBN_F_HEAD_MFMA head fragments); [5] = wblk_off, [6] =
- * wblk_len: the NN CPD's weight block [W1 fragments | layer-1/2 accumulator-init biases |
- * split-f16 W2 | W3 | b3], rounded up to a multiple of 256 floats (params float offset,
- * length in floats), which the walk stages into LDS one step ahead (0 = the step runs no
- * MLP); the exact-f32 W2 copy (off_w2) deliberately stays outside the block and is read from
- * global memory on the rare exact path; [7] = (ABI v12) kde steps: the one-feature moment
- * table of pass 1 (plan.py kde_moment_table: header of 8 floats [u_lo, 1/delta, delta, n_cells,
- * n_chunks, chunk points (int32 bits), 0, 0] then [n_cells][n_chunks + n_groups + 1][4 terms]
- * f32: the chunks, their groups of 8, the whole point set), -1 = none; -1 on every other step.
- * off_w1 on kde steps (an NN field otherwise): the two-feature moment table of pass 1 (plan.py
- * kde_moment_table2: header of 16 floats -- per feature [u_lo, 1/delta, delta, n_cells (int32
- * bits)], then rows per cell, floats per row, K (int32 bits), zeros -- then [n_cells0 *
- * n_cells1][rows][48] f32, rows = the 16 chunks of the MFMA pass and, where that pass keeps
- * half sums, the first half of each; a row = the 45 coefficients T[a,b], a + b < 9, in the
- * order of csrc kde_mt2_row's nested Horner, padded to 16 bytes), -1 = none.
- * KDE packs [1] (parent features) and
- * [2] (parent ++ target features) hold the bf16x3 slots of v_mfma_f32_16x16x32_bf16
- * ([block][quarter][16 points][8 bf16], plan.py _kde_pack_bf16); [3] = per-point f32 records,
- * [4] = the packed-VALU layout. */
+/* Kind-set bits: which walk instantiation runs a plan (vbn_walk_args.kind_mask holds the plan's
+ * part, the launcher adds the launch form; csrc/vbn_walk_kernel.h VBN_WALK_KIND_SETS lists the
+ * instantiated sets).  Bits 0-4 = 1 << vbn_kind of every CPD kind walked. */
+#define VBN_KM_NONRELU 32        /* some NN CPD has a non-relu activation                      */
+#define VBN_KM_HALFWAVE 64       /* half-wave (mirror) launch, wave_particles = 32             */
+#define VBN_KM_LEAN 128          /* no injected draws, no segment state, not Gibbs             */
+#define VBN_KM_NOISELESS 256     /* no injected draws (production Gibbs sweeps)                */
+#define VBN_KM_GENERIC_MLP 512   /* some NN CPD has hidden_dims other than (32, 32)            */
+#define VBN_KM_TABLE 1024        /* alone: every step is a categorical_table (vbn_hip_table_walk) */
+#define VBN_KM_KINDS 63          /* the plan's CPD kinds and VBN_KM_NONRELU                    */
+#define VBN_KM_NN_KINDS 21       /* any NN kind: gaussian_nn | mdn | softmax_nn                */
+#define VBN_KM_UNSTAGED_KINDS 28 /* mdn | kde | softmax_nn: sets that read weights from the blob */
+
+/* One node of the topological walk (32 x int32, filled by the host plan packer; offsets are float
+ * offsets into the parameter blob).  The layout is frozen: recorded plans index rows by number.
+ * Three words mean something else on another step kind; csrc/vbn_walk_common.h names those
+ * readings (step_zlim, step_off_w3h, step_off_kmt2). */
 typedef struct vbn_step {
   int32_t kind, role, flags, act;
   int32_t n_in, in_off, out_col, out_dim;
   int32_t fixed_col, k, n_out, node_id;
   int32_t noise_idx, aux0, aux1, aux2;
-  int32_t off_std, off_w1, off_w2, off_b2, off_w3, off_b3, off_tail, off_pts;
-  int32_t reserved[8];
+  int32_t off_std;
+  int32_t off_w1;    /* NN: W1 fragments.  kde: the two-feature moment table of pass 1, -1 = none */
+  int32_t off_w2;    /* exact-f32 W2 copy: outside the weight block, read from global memory on
+                        the rare exact path */
+  int32_t off_b2, off_w3, off_b3, off_tail, off_pts;
+  int32_t off_w2h;   /* split-f16 W2 fragments */
+  int32_t off_kq;    /* kde: bf16x3 parent pack ([block][quarter][16 points][8 bf16], the slots of
+                        v_mfma_f32_16x16x32_bf16), -1 = none.  NN: f32 bits of the layer-1
+                        operand bound zlim */
+  int32_t off_kqy;   /* kde: bf16x3 parent ++ target pack, -1 = none.  NN with VBN_F_HEAD_MFMA:
+                        the head fragments */
+  int32_t off_kr;    /* kde: per-point f32 records */
+  int32_t off_kv;    /* kde: packed-VALU layout */
+  int32_t wblk_off;  /* NN: the weight block [W1 fragments | layer-1/2 accumulator-init biases |
+                        split-f16 W2 | W3 | b3], rounded up to a multiple of 256 floats, which the
+                        walk stages into LDS one step ahead */
+  int32_t wblk_len;  /* its length in floats; 0 = the step runs no MLP */
+  int32_t off_kmt;   /* kde: the one-feature moment table of pass 1, -1 = none; -1 on every other
+                        step */
 } vbn_step;
+
+#ifdef __cplusplus
+#define VBN_STATIC_ASSERT(c, m) static_assert(c, m)
+#else
+#define VBN_STATIC_ASSERT(c, m) _Static_assert(c, m)
+#endif
+VBN_STATIC_ASSERT(sizeof(vbn_step) == 128, "vbn_step is 32 int32");
+VBN_STATIC_ASSERT(__builtin_offsetof(vbn_step, wblk_len) == 120, "vbn_step.wblk_len is word 30");
+VBN_STATIC_ASSERT(__builtin_offsetof(vbn_step, off_kmt) == 124, "vbn_step.off_kmt is word 31");
 
 /* Arguments of one particle walk over B queries x S samples. */
 typedef struct vbn_walk_args {
@@ -144,9 +166,8 @@ typedef struct vbn_walk_args {
   int32_t dmax;
   int32_t n_out_cols;
   int32_t mode;            /* enum vbn_mode                                        */
-  int32_t kind_mask;       /* CPD kinds walked: 1<<kind, | 32 if a non-relu activation,
-                              | 512 if some NN CPD has hidden_dims other than (32, 32);
-                              1024 alone: every step is a categorical_table
+  int32_t kind_mask;       /* CPD kinds walked: 1<<kind, | VBN_KM_NONRELU, | VBN_KM_GENERIC_MLP;
+                              VBN_KM_TABLE alone: every step is a categorical_table
                               (vbn_hip_table_walk; vbn_hip_walk refuses it)             */
   int64_t q_base;          /* global index of query 0 (multi-GPU shards)            */
   uint64_t seed;

@@ -29,7 +29,7 @@ def main():
         return gibbs_variants(a.variants)
     import bench
     from vectorizedbayesiannetwork_amd import jit
-    from vectorizedbayesiannetwork_amd.plan import MODE_MCM, MODE_WEIGHTED, PackedModel, build_plan
+    from vectorizedbayesiannetwork_amd.plan import KM_LEAN, MODE_MCM, MODE_WEIGHTED, PackedModel, build_plan
     cfg, model, target, ev = bench.build_model(a.config)
     pk = PackedModel(model, "cpu")
     vals = set(ev)
@@ -41,7 +41,7 @@ def main():
     else:
         plan = build_plan(pk, latent=lat, fixed=fix, logp=[target], out_nodes=[target], shared_roots=True,
                           mode=MODE_MCM)
-    km = plan.kind_mask | 128
+    km = plan.kind_mask | KM_LEAN
     steps, ic, _ = plan.steps._vbn_host
     src = jit.plan_source(steps, ic, km)
     os.makedirs(os.path.join(REPO, a.outdir), exist_ok=True)
@@ -61,7 +61,7 @@ def main():
 def gibbs_variants(variants):
     import bench
     from vectorizedbayesiannetwork_amd import jit
-    from vectorizedbayesiannetwork_amd.plan import PackedModel, build_gibbs_plan
+    from vectorizedbayesiannetwork_amd.plan import KM_NOISELESS, PackedModel, build_gibbs_plan
     cfg, model, target, ev = bench.build_model("cfg2")
     pk = PackedModel(model, "cpu")
     vals = set(ev)
@@ -72,7 +72,7 @@ def gibbs_variants(variants):
     # chain workgroups of ops.CHAIN_WAVES waves on the cost model's schedule
     from vectorizedbayesiannetwork_amd import ops
     from vectorizedbayesiannetwork_amd.plan import gibbs_schedule
-    km = gp.kind_mask | 256
+    km = gp.kind_mask | KM_NOISELESS
     src = jit.plan_source(steps, ic, km, gibbs_schedule(steps, ic, ops.CHAIN_WAVES))
     base = jit.OPTIONS
     for v in variants:

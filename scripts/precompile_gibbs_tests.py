@@ -5,7 +5,7 @@ package's plan cache, so `pytest -m gpu` on a fresh box does not spend minutes i
     python scripts/precompile_gibbs_tests.py
 
 The kind set of each launch is the library's own (`vbn_hip_walk_kind_set` on the arguments
-`ops.gibbs_walk` builds, | 256 without injected draws) and the schedule is `plan.gibbs_schedule`
+`ops.gibbs_walk` builds, | KM_NOISELESS without injected draws) and the schedule is `plan.gibbs_schedule`
 with the test's `VBN_GIBBS_SPLIT`, so the source -- and the cache key -- are the ones
 `jit.module_for` computes.  A unit the tests no longer load only costs disk.
 """
@@ -33,7 +33,7 @@ CFG2_CASES = [(32, 1, ""), (32, 2, ""), (32, 4, ""), (64, 1, ""), (64, 2, ""), (
 
 def _kind_set(gp, pk, n_chains, wp, noise):
     from vectorizedbayesiannetwork_amd import _lib
-    from vectorizedbayesiannetwork_amd.plan import MODE_GIBBS
+    from vectorizedbayesiannetwork_amd.plan import KM_NOISELESS, MODE_GIBBS
     import torch
     lib = _lib.load()
     dummy = torch.zeros(16)
@@ -51,7 +51,7 @@ def _kind_set(gp, pk, n_chains, wp, noise):
     km = lib.vbn_hip_walk_kind_set(ctypes.byref(a))
     if km <= 0:
         raise RuntimeError(f"kind set: error {km}")
-    return km | (0 if noise else 256)              # ops._plan_module
+    return km | (0 if noise else KM_NOISELESS)              # ops._plan_module
 
 
 def _units():

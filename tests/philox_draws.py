@@ -1,7 +1,7 @@
 """Host replica of the HIP walk's production RNG, as a draw provider for the oracle.
 
 The production ("lean") walk never reads injected draws: each latent step makes its own
-draws from counter-based Philox-2x32-10 (csrc/vbn_walk_impl.h ``rng_words``,
+draws from counter-based Philox-2x32-10 (csrc/vbn_walk_common.h ``rng_words``,
 ``draw_normal``, ``draw_uniforms``).  :class:`PhiloxDraws` recomputes exactly those words on
 the host and hands them to the oracle (oracle/vbn_oracle.py) through the same
 ``normal / uniform / categorical / randint`` calls the reference makes, so the oracle runs

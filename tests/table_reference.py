@@ -15,7 +15,7 @@ Draws come from a provider with ``categorical(node, probs [Bq, S, D, C], shared,
 * :class:`ReplayDraws` replays a fixture's recorded class indices (make_golden.Recorder: one
   ``cat`` record per CPD call, flattened [b, s, d]);
 * :class:`PhiloxTableDraws` recomputes the table walk's production draws: stream 1, word 0 of
-  ``rng_words`` (csrc/vbn_walk_impl.h) keyed by (seed, offset, node id, dim, query key -- 0 for
+  ``rng_words`` (csrc/vbn_walk_common.h) keyed by (seed, offset, node id, dim, query key -- 0 for
   shared root draws --, sample), and picks "the smallest k with cdf[k] > u * total, else C - 1"
   on the float64 CDF of the float64 probabilities.
 

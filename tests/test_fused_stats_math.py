@@ -1,4 +1,4 @@
-"""Host replica of the fused posterior summary's arithmetic (csrc vbn_walk_impl.h stats_partials:
+"""Host replica of the fused posterior summary's arithmetic (csrc vbn_walk_kernel.h stats_partials:
 per-64-particle float64 rows; vbn_walk.hip vbn_stats_merge_kernel: Chan's pairwise merge) against
 the oracle's VBN._posterior_stats (vbn.py:483-504) -- the decomposition itself, on CPU, including
 zero-weight waves, all-zero rows (uniform weights) and NaN samples.  The GPU kernels are checked

@@ -286,15 +286,15 @@ def test_chain_sweep_source():
                             fixed=[n for n in model.topo if n in ev], target=target)
     rows, ic, _ = gp.steps._vbn_host
     phases, n_rows = P.gibbs_schedule(rows, ic, 4)
-    src = jit.plan_source(rows, ic, gp.kind_mask | 64 | 256, (phases, n_rows))
+    src = jit.plan_source(rows, ic, gp.kind_mask | P.KM_HALFWAVE | P.KM_NOISELESS, (phases, n_rows))
     assert "#define VBN_PLAN_CHAIN_WAVES 4" in src
     assert f"__shared__ float vbn_lp_rows[{n_rows} * WAVE];" in src
     assert src.count("__syncthreads();") == len(phases)
     idx = [int(x) for x in re.findall(r"vbn_plan_step_(?:direct|lpout|select)<KM, ([0-9]+)", src)]
     assert sorted(idx) == list(range(len(rows)))
-    assert "VBN_PLAN_CHAIN_WAVES" not in jit.plan_source(rows, ic, gp.kind_mask | 64 | 256)
+    assert "VBN_PLAN_CHAIN_WAVES" not in jit.plan_source(rows, ic, gp.kind_mask | P.KM_HALFWAVE | P.KM_NOISELESS)
     assert "__launch_bounds__(4 * WAVE)" in src
-    src8 = jit.plan_source(rows, ic, gp.kind_mask | 256, P.gibbs_schedule(rows, ic, 8))
+    src8 = jit.plan_source(rows, ic, gp.kind_mask | P.KM_NOISELESS, P.gibbs_schedule(rows, ic, 8))
     assert "#define VBN_PLAN_CHAIN_WAVES 8" in src8 and "__launch_bounds__(8 * WAVE)" in src8
 
 

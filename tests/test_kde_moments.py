@@ -138,7 +138,7 @@ def test_moment_table_declines_wide_data():
 
 def test_cfg4_one_feature_steps_carry_tables():
     """The packed cfg4 model (reference-fitted, M = 10,000): every one-parent KDE node has a
-    moment table (step reserved[7] = its blob offset), every other node -1; the table's rows
+    moment table (step off_kmt = its blob offset), every other node -1; the table's rows
     match the exact sums at the node's own data points; such nodes are not precomputed (the
     table makes their chunk sums cheap in the walk)."""
     import bench
@@ -168,18 +168,18 @@ def test_cfg4_one_feature_steps_carry_tables():
         u = np.float32(2.0) * (c_p * np.float32(x))
         got, (ref, _) = _kernel_rows(tab, u), _exact_rows(y, u, nch, per)
         assert np.max(np.abs(got - ref) / ref) <= 4e-7
-    # plan rows: reserved[7] holds the offset for those nodes, -1 elsewhere; none precomputed
+    # plan rows: off_kmt holds the offset for those nodes, -1 elsewhere; none precomputed
     latent = [n for n in model.topo if n not in ev]
     plan = P.build_plan(pk, latent=latent, fixed=[n for n in model.topo if n in ev],
                         out_nodes=[target], logp=[target], skip=[], shared_roots=True, mode=P.MODE_MCM)
     rows = plan.steps._vbn_host[0]
     for r in rows:
         if r[P.S_KIND] == P.KIND_ID["kde"] and r[P.S_AUX0] == 1:
-            assert r[P.S_RES7] > 0
+            assert r[P.S_OFF_KMT] > 0
         else:
-            assert r[P.S_RES7] == -1
+            assert r[P.S_OFF_KMT] == -1
     pc = P.precompute_plans(pk, plan)
     assert pc is not None
     for r in pc[0].steps._vbn_host[0]:
-        if r[P.S_RES7] >= 0:
+        if r[P.S_OFF_KMT] >= 0:
             assert not r[P.S_FLAGS] & P.F_PRECOMP

@@ -214,7 +214,7 @@ def test_moment2_table_declines_wide_data():
 
 def test_cfg4_two_feature_steps_carry_tables():
     """The packed cfg4 model (M = 10,000): every two-parent KDE node has a 2-D table (step
-    off_w1 = its blob offset), every other step -1 there; reserved[7] still holds the one-feature
+    off_w1 = its blob offset), every other step -1 there; off_kmt still holds the one-feature
     tables only; the rows match the exact sums at the node's own data points; x9 and x41 stay
     precomputed (per sample / per query) and keep their 17 floats."""
     import bench
@@ -247,8 +247,8 @@ def test_cfg4_two_feature_steps_carry_tables():
     for r in plan.steps._vbn_host[0]:
         n = name_of[int(r[P.S_NODEID])]
         assert r[P.S_KIND] == P.KIND_ID["kde"]           # cfg4 is a KDE DAG: every step
-        assert r[P.S_OFF_W1] == (pk.nodes[n].offs["kmt2"] if n in two else -1), n
-        assert r[P.S_RES7] == pk.nodes[n].offs.get("kmt", -1), n
+        assert r[P.S_OFF_KMT2] == (pk.nodes[n].offs["kmt2"] if n in two else -1), n
+        assert r[P.S_OFF_KMT] == pk.nodes[n].offs.get("kmt", -1), n
     pc = P.precompute_plans(pk, plan)
     assert pc is not None
     pre = {name_of[int(r[P.S_NODEID])] for r in pc[0].steps._vbn_host[0] if r[P.S_FLAGS] & P.F_PRECOMP}

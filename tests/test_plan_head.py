@@ -6,7 +6,7 @@ import pytest
 from vectorizedbayesiannetwork_amd import synthetic
 from vectorizedbayesiannetwork_amd.model import random_init_model
 from vectorizedbayesiannetwork_amd.plan import (F_HEAD_MFMA, MODE_WEIGHTED, S_FLAGS, S_KIND,
-                                                S_NOUT, S_OFF_KQ, S_OFF_KQY, PackedModel, _ROWS, build_plan)
+                                                S_NOUT, S_OFF_W3H, S_ZLIM, PackedModel, _ROWS, build_plan)
 
 
 def _model():
@@ -43,7 +43,7 @@ def test_wide_heads_carry_mfma_fragments(monkeypatch):
         if not wide:
             continue
         seen += 1
-        off = int(r[S_OFF_KQY])
+        off = int(r[S_OFF_W3H])
         assert off == pk.nodes[n].offs["w3h"] and off >= 0
         frag = blob[off:off + 1024].view(np.float16).reshape(4, 64, 8).astype(np.float32)
         (w3, b3) = [(np.asarray(w, np.float32), np.asarray(b, np.float32)) for w, b in rec.mlp_layers()[-1:]][0]
@@ -71,7 +71,7 @@ def test_layer1_operand_bound_is_conservative():
     for i, n in enumerate(model.topo):
         if not model.parents[n] or "zlim" not in pk.nodes[n].offs:
             continue
-        zlim = steps[i, S_OFF_KQ:S_OFF_KQ + 1].view(np.float32)[0]
+        zlim = steps[i, S_ZLIM:S_ZLIM + 1].view(np.float32)[0]
         assert zlim == np.float32(pk.nodes[n].offs["zlim"])
         w1, b1 = [np.asarray(t, np.float64) for t in model.cpds[n].mlp_layers()[0]]
         if zlim <= 0:

@@ -35,7 +35,7 @@ def _want(model, vals, plan, shared):
     ws, wq = set(), set()
     for i, n in enumerate(model.topo):
         kind = model.cpds[n].kind
-        if not model.parents[n] or kind not in NN_KDE or (kind == "kde" and rows[i][P.S_RES7] >= 0):
+        if not model.parents[n] or kind not in NN_KDE or (kind == "kde" and rows[i][P.S_OFF_KMT] >= 0):
             continue
         latent = n not in vals
         if not latent and not (kind != "kde" and rows[i][P.S_FLAGS] & P.F_LOGP):

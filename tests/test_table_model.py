@@ -180,7 +180,7 @@ def test_other_models_keep_their_plans():
     pk = P.PackedModel(model_from_checkpoint(other), torch.device("cpu"))
     plan = P.build_plan(pk, latent=list(pk.model.topo), fixed=[], logp=[], out_nodes=[pk.model.topo[-1]],
                         shared_roots=True, mode=P.MODE_SAMPLE)
-    assert not pk.tabular and not plan.tabular and plan.table_out_cols is None and not plan.kind_mask & 1024
+    assert not pk.tabular and not plan.tabular and plan.table_out_cols is None and not plan.kind_mask & P.KM_TABLE
 
 
 def test_random_table_model_is_seeded_and_loads():

@@ -2,7 +2,7 @@
 // categorical_table (reference vbn/cpds/categorical_table.py:359-417: _logits_from_parents,
 // sample, log_prob), and its C-ABI entry vbn_hip_table_walk (include/vbn_hip.h).
 //
-// Lane = particle, wave64, as in vbn_walk_impl.h; the step table, roles, flags, modes, evidence
+// Lane = particle, wave64, as in vbn_walk_kernel.h; the step table, roles, flags, modes, evidence
 // buffer, injected draws and Philox keying are the walk's (rng_words / u01 of that header).  A
 // node's state is its class INDEX per output dim, kept in LDS slots idx[slot][64] (rows are
 // lane-contiguous: no bank conflicts; a lane only ever reads its own column, so the steps need no
@@ -31,7 +31,7 @@
 // global_load_lds_dwordx4 and gathered from there; larger blobs are gathered from global / L2.
 // Both paths read the same floats and run the same arithmetic: identical outputs.
 #include "vbn_hip.h"
-#include "vbn_walk_impl.h"
+#include "vbn_walk_common.h"
 
 #include <stdlib.h>
 
@@ -193,7 +193,7 @@ static int tw_check(const vbn_walk_args* a) {
   if (!a || (!a->steps && a->n_steps > 0) || a->n_steps < 0 || !a->params || a->n_samples <= 0 ||
       a->n_queries <= 0 || a->n_slots <= 0 || !a->in_cols)
     return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: bad arguments");
-  if (a->kind_mask != 1024)
+  if (a->kind_mask != VBN_KM_TABLE)
     return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: only plans whose every step is a categorical_table "
                                 "(kind_mask 1024)");
   if (a->state || a->state_flags || a->precomp_q || a->stats_part || a->wave_particles == 32 ||

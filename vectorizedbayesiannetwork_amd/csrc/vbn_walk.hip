@@ -637,7 +637,7 @@ static int walk_shape(const vbn_walk_args* a, walk_launch* out) {
     return fail(VBN_E_ARGS, "vbn_hip_walk: bad arguments");
   if (a->out_x && (!a->out_cols || a->n_out_cols <= 0))
     return fail(VBN_E_ARGS, "vbn_hip_walk: out_x without out_cols");
-  if ((unsigned)a->kind_mask & ~1023u)
+  if ((unsigned)a->kind_mask & ~(VBN_KM_TABLE - 1u))
     return fail(VBN_E_ARGS, "vbn_hip_walk: categorical_table plans (kind_mask 1024) run on vbn_hip_table_walk");
   if ((a->state_flags & 4) && (!a->state || a->state_flags != 4 || a->noise || a->mode == VBN_MODE_GIBBS))
     return fail(VBN_E_ARGS, "vbn_hip_walk: state_flags 4 (precomputed per-sample quantities) needs a state "
@@ -657,15 +657,15 @@ static int walk_shape(const vbn_walk_args* a, walk_launch* out) {
   const int64_t wp = a->wave_particles == 32 ? 32 : WAVE;   // particles per wave
   // smallest instantiated kind set covering the plan (VBN_WALK_KIND_SETS)
   static const unsigned masks[] = {1u, 2u, 3u, 4u, 8u, 16u, 20u, 23u, 31u, 63u};
-  const unsigned want = (unsigned)a->kind_mask & 63u;
-  unsigned km = 63u;
+  const unsigned want = (unsigned)a->kind_mask & VBN_KM_KINDS;
+  unsigned km = VBN_KM_KINDS;
   for (unsigned m : masks) {
     if ((m & want) == want && __builtin_popcount(m) < __builtin_popcount(km)) km = m;
   }
-  const bool generic = ((unsigned)a->kind_mask & 512u) != 0;   // some MLP with other hidden_dims
-  if (generic) km = 63u;
+  const bool generic = ((unsigned)a->kind_mask & VBN_KM_GENERIC_MLP) != 0;   // some MLP with other hidden_dims
+  if (generic) km = VBN_KM_KINDS;
 #ifdef VBN_KM_ONLY
-  km = VBN_KM_ONLY & 63u;
+  km = VBN_KM_ONLY & VBN_KM_KINDS;
 #endif
   // waves per workgroup: staged kind sets take the most resident waves per CU (160 KiB LDS,
   // 16 waves = 4 per SIMD at the kernel's register budget), larger workgroups on ties (one
@@ -693,7 +693,7 @@ static int walk_shape(const vbn_walk_args* a, walk_launch* out) {
   if (stage && nw == 0) {
     // the two LDS weight buffers do not fit next to the value slots (very wide MLP fan-in):
     // run the smallest unstaged kind set covering the plan, which reads weights from the blob
-    km = ((want & 32u) || generic) ? 63u : 23u;
+    km = ((want & VBN_KM_NONRELU) || generic) ? VBN_KM_KINDS : 23u;
     stage = false;
     shape(false);
   }
@@ -706,13 +706,12 @@ static int walk_shape(const vbn_walk_args* a, walk_launch* out) {
   const int64_t total = a->n_queries * (int64_t)a->n_samples;
   const int64_t blocks = (total + wp * nw - 1) / (wp * nw);
   if (blocks > 0x7fffffffLL) return fail(VBN_E_ARGS, "vbn_hip_walk: too many particles for one launch");
-  // kind set | 64: the half-wave (mirror) instantiation; | 128: the lean one
   // lean: no injected draws, no segment state (state_flags 4 = read-only per-sample quantities
   // of VBN_F_PRECOMP steps, which the lean walk reads), not Gibbs
   const bool lean = !a->noise && (!a->state || a->state_flags == 4) && a->mode != VBN_MODE_GIBBS;
-  out->kmi = km | (wp == 32 ? 64u : 0u) | (lean && wp != 32 ? 128u : 0u) |
-             (wp == 32 && !a->noise ? 256u : 0u) |  // | 256: half-wave without injected draws
-             (generic ? 512u : 0u);                 // | 512: with the generic-MLP path
+  out->kmi = km | (wp == 32 ? VBN_KM_HALFWAVE : 0) | (lean && wp != 32 ? VBN_KM_LEAN : 0) |
+             (wp == 32 && !a->noise ? VBN_KM_NOISELESS : 0) |   // half-wave without injected draws
+             (generic ? VBN_KM_GENERIC_MLP : 0);
   out->grid = dim3((unsigned)blocks);
   out->block = dim3(WAVE * nw);
   out->lds = (size_t)lds;
@@ -734,11 +733,11 @@ extern "C" int vbn_hip_walk(const vbn_walk_args* a, void* stream) {
 #ifdef VBN_KM_ONLY
   // experiment builds (make exp KM=...): one instantiation only
   // (a lean-less set may serve a lean launch; never the reverse)
-  const unsigned want = (unsigned)a->kind_mask & 63u;
-  const bool lean = (w.kmi & 128u) != 0;
+  const unsigned want = (unsigned)a->kind_mask & VBN_KM_KINDS;
+  const bool lean = (w.kmi & VBN_KM_LEAN) != 0;
   const int64_t wp = a->wave_particles == 32 ? 32 : WAVE;
-  if ((VBN_KM_ONLY & want) != want || ((VBN_KM_ONLY & 64) != 0) != (wp == 32) || ((VBN_KM_ONLY & 128) && !lean) ||
-      ((VBN_KM_ONLY & 256) && a->noise))
+  if ((VBN_KM_ONLY & want) != want || ((VBN_KM_ONLY & VBN_KM_HALFWAVE) != 0) != (wp == 32) ||
+      ((VBN_KM_ONLY & VBN_KM_LEAN) && !lean) || ((VBN_KM_ONLY & VBN_KM_NOISELESS) && a->noise))
     return fail(VBN_E_ARGS, "vbn_hip_walk: kind set not built in this experiment library");
   e = VBN_LAUNCHER(VBN_KM_ONLY)(a, w.grid, w.block, w.lds, st);
 #else
@@ -810,10 +809,10 @@ extern "C" int vbn_hip_walk_module(const void* handle, const vbn_walk_args* a, v
   walk_launch w;
   const int rc = walk_shape(a, &w);
   if (rc) return rc;
-  // a Gibbs sweep without injected draws may run the draw-free (| 256) unit at full wave too:
-  // the interpreter instantiates | 256 for half waves only, a plan unit is compiled per set
+  // a Gibbs sweep without injected draws may run the draw-free (| VBN_KM_NOISELESS) unit at full wave
+  // too: the interpreter instantiates it for half waves only, a plan unit is compiled per set
   // (full-wave cfg2 sweep: 97 VGPR spills with the injected-draw paths, none without)
-  const unsigned free_km = w.kmi | ((a->mode == VBN_MODE_GIBBS && !a->noise) ? 256u : 0u);
+  const unsigned free_km = w.kmi | ((a->mode == VBN_MODE_GIBBS && !a->noise) ? VBN_KM_NOISELESS : 0);
   if ((m->kmi != w.kmi && m->kmi != free_km) || a->n_steps != m->n_steps)
     return fail(VBN_E_ARGS, "vbn_hip_walk_module: the launch does not match the compiled plan (kind set / steps)");
   if (m->chain_waves > 0) {

@@ -24,7 +24,7 @@ struct vbn_seq {};
 
 constexpr int vbn_plan_next_mlp(int j) {
   for (; j < VBN_PLAN_N_STEPS; ++j)
-    if (VBN_PLAN_STEPS[j].reserved[6] > 0) return j;
+    if (VBN_PLAN_STEPS[j].wblk_len > 0) return j;
   return -1;
 }
 
@@ -32,14 +32,14 @@ constexpr int vbn_plan_next_mlp(int j) {
 constexpr int vbn_plan_parity(int i) {
   int par = 0;
   for (int j = 0; j < i; ++j)
-    if (VBN_PLAN_STEPS[j].reserved[6] > 0) par ^= 1;
+    if (VBN_PLAN_STEPS[j].wblk_len > 0) par ^= 1;
   return par;
 }
 
 template <int J>
 __device__ __forceinline__ void vbn_plan_stage(const vbn_walk_args& A, const float* __restrict__ params, float* wbuf,
                                                int buf, int wave, int nw, int lane) {
-  constexpr int off = VBN_PLAN_STEPS[J].reserved[5], len = VBN_PLAN_STEPS[J].reserved[6];
+  constexpr int off = VBN_PLAN_STEPS[J].wblk_off, len = VBN_PLAN_STEPS[J].wblk_len;
   float* dst = wbuf + buf * A.wbuf_floats;
   for (int c = wave; c * WBLK_CHUNK < len; c += nw)
     __builtin_amdgcn_global_load_lds((const void*)(params + off + c * WBLK_CHUNK + lane * 4),
@@ -55,7 +55,7 @@ __device__ __forceinline__ void vbn_plan_step(const vbn_walk_args& A, const floa
                                               int wave, int nw, Lane& L, float& lp, int& par, bool more) {
   constexpr vbn_step st = VBN_PLAN_STEPS[I];
   if constexpr (staged_kinds(KM)) {
-    if constexpr (st.reserved[6] > 0) {
+    if constexpr (st.wblk_len > 0) {
       step_barrier();
       constexpr int nxt = vbn_plan_next_mlp(I + 1);
       if constexpr (nxt >= 0) {
@@ -67,7 +67,7 @@ __device__ __forceinline__ void vbn_plan_step(const vbn_walk_args& A, const floa
       par ^= 1;
     }
   } else {
-    L.wb = params + st.reserved[5];
+    L.wb = params + st.wblk_off;
   }
   walk_step<KM>(A, st, L, lp);
 }
@@ -85,14 +85,14 @@ __device__ __forceinline__ void vbn_plan_step_lean(const vbn_walk_args& A, const
                                                    float* wbuf, int wave, int nw, Lane& L, float& lp) {
   constexpr vbn_step st = VBN_PLAN_STEPS[I];
   if constexpr (staged_kinds(KM)) {
-    if constexpr (st.reserved[6] > 0) {
+    if constexpr (st.wblk_len > 0) {
       step_barrier();
       constexpr int nxt = vbn_plan_next_mlp(I + 1);
       if constexpr (nxt >= 0) vbn_plan_stage<nxt>(A, params, wbuf, vbn_plan_parity(I) ^ 1, wave, nw, L.lane);
       L.wb = wbuf + vbn_plan_parity(I) * A.wbuf_floats;
     }
   } else {
-    L.wb = params + st.reserved[5];
+    L.wb = params + st.wblk_off;
   }
   walk_step<KM>(A, st, L, lp);
 }
@@ -123,9 +123,9 @@ __device__ __forceinline__ void vbn_walk_plan_general(const vbn_walk_args& A, co
   L.scr = L.vals + A.n_slots * WAVE;
   L.wb = wbuf;
   const int64_t total = A.n_queries * (int64_t)A.n_samples;
-  L.mirror = (KM & 64) != 0;
-  L.lean = (KM & 128) != 0;
-  L.noiseless = (KM & (128 | 256)) != 0;
+  L.mirror = (KM & VBN_KM_HALFWAVE) != 0;
+  L.lean = (KM & VBN_KM_LEAN) != 0;
+  L.noiseless = (KM & (VBN_KM_LEAN | VBN_KM_NOISELESS)) != 0;
   L.bm_spare = 0.f;
   const int wp = L.mirror ? 32 : WAVE;
   L.wq = A.mode != VBN_MODE_GIBBS && (A.n_samples & (wp - 1)) == 0;
@@ -195,7 +195,7 @@ template <unsigned KM, int I>
 __device__ __forceinline__ void vbn_plan_step_direct(const vbn_walk_args& A, const float* __restrict__ params,
                                                      Lane& L, float& lp) {
   constexpr vbn_step st = VBN_PLAN_STEPS[I];
-  L.wb = params + st.reserved[5];
+  L.wb = params + st.wblk_off;
   walk_step<KM>(A, st, L, lp);
 }
 
@@ -223,9 +223,9 @@ __device__ __forceinline__ void vbn_walk_plan_chains(const vbn_walk_args& A, con
   L.scr = smem + A.n_slots * WAVE + wave * rows * WAVE;   // per-wave head / scratch rows
   L.wb = params;
   const int64_t total = A.n_queries * (int64_t)A.n_samples;
-  L.mirror = (KM & 64) != 0;
+  L.mirror = (KM & VBN_KM_HALFWAVE) != 0;
   L.lean = false;
-  L.noiseless = (KM & 256) != 0;
+  L.noiseless = (KM & VBN_KM_NOISELESS) != 0;
   L.bm_spare = 0.f;
   L.wq = false;
   const int wp = L.mirror ? 32 : WAVE;
@@ -259,7 +259,7 @@ __device__ __forceinline__ void vbn_walk_plan_chains(const vbn_walk_args& A, con
 
 template <unsigned KM>
 __device__ __forceinline__ void vbn_walk_plan_body(const vbn_walk_args& A, const float* __restrict__ params) {
-  if constexpr ((KM & 128u) != 0) {      // lean (production MCM / IS / LW / ancestral): one pass
+  if constexpr ((KM & VBN_KM_LEAN) != 0) {   // lean (production MCM / IS / LW / ancestral): one pass
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int nw = blockDim.x >> 6, wave = threadIdx.x >> 6;
     const int per_wave = (A.n_slots + (A.max_out > 0 ? A.max_out : 1)) * WAVE;

@@ -43,8 +43,8 @@ import torch
 
 from . import ops
 from .model import BNModel, model_from_vbn
-from .plan import (F_PRE_OUT, KIND_ID, MODE_MCM, MODE_SAMPLE, MODE_WEIGHTED, S_FLAGS, S_KIND, GibbsPlan, PackedModel,
-                   QueryPlan, barren_pruned,
+from .plan import (F_PRE_OUT, KIND_ID, KM_GENERIC_MLP, KM_UNSTAGED_KINDS, MODE_MCM, MODE_SAMPLE, MODE_WEIGHTED,
+                   S_FLAGS, S_KIND, GibbsPlan, PackedModel, QueryPlan, barren_pruned,
                    liveness_order, precompute_plans,
                    build_gibbs_plan, build_plan)
 from .registry import register_inference, register_sampling
@@ -163,7 +163,7 @@ def _resident_waves(p: QueryPlan) -> int:
     that stage MLP weights in LDS (only gaussian_nn / linear_gaussian, no generic MLP shapes:
     staged_kinds), two weight buffers of ``wbuf`` floats per workgroup of 4, 2 or 1 waves."""
     per_wave = (p.n_slots + max(p.max_out, 1)) * 64 * 4
-    staged = (p.kind_mask & 28) == 0 and not (p.kind_mask & 512)
+    staged = (p.kind_mask & KM_UNSTAGED_KINDS) == 0 and not (p.kind_mask & KM_GENERIC_MLP)
     best = 0
     for w in ((4, 2, 1) if staged else (1,)):
         lds = w * per_wave + (2 * p.wbuf * 4 if staged else 0)

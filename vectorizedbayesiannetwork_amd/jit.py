@@ -34,6 +34,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import _lib
+from .plan import KIND_ID, KM_LEAN, STEP_INTS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -63,10 +64,8 @@ def plan_source(steps: np.ndarray, in_cols: np.ndarray, kind_set: int, schedule=
     """The translation unit of one plan-specialised walk (csrc/vbn_walk_plan.h).  ``schedule``
     (plan.gibbs_schedule: (phases, n_rows), per phase the ops of each wave) makes it a Gibbs
     sweep on chain workgroups of ``len(phases[0])`` waves."""
-    rows = []
-    for r in np.asarray(steps, np.int32).reshape(-1, 32):
-        v = [int(x) for x in r]
-        rows.append("  {" + ", ".join(map(str, v[:24])) + ", {" + ", ".join(map(str, v[24:])) + "}},")
+    rows = ["  {" + ", ".join(str(int(x)) for x in r) + "},"
+            for r in np.asarray(steps, np.int32).reshape(-1, STEP_INTS)]
     ic = [int(x) for x in np.asarray(in_cols, np.int32).reshape(-1)] or [0]
     chain, sweep = [], []
     if schedule:
@@ -115,8 +114,9 @@ def plan_source(steps: np.ndarray, in_cols: np.ndarray, kind_set: int, schedule=
     # 41 spills, ~0.8 GB of scratch traffic per launch at 4 waves per SIMD) run at 3 waves per
     # SIMD without spills -- measured equal time (1.792 vs 1.794 ms, profiles/r05_bench/
     # r05f_ab_cfg3.txt); KDE kind sets keep 4 waves (their exp stream needs the occupancy)
-    wpe = (["#define VBN_WPE 3"] if (kind_set & 128) and (kind_set & 20) and not (kind_set & 8) and not schedule
-           else [])
+    wide_heads, kde = (1 << KIND_ID["mdn"]) | (1 << KIND_ID["softmax_nn"]), 1 << KIND_ID["kde"]
+    wpe = (["#define VBN_WPE 3"] if (kind_set & KM_LEAN) and (kind_set & wide_heads) and not (kind_set & kde)
+                                    and not schedule else [])
     # chain workgroups may run up to 8 waves (vbn_hip_module_chain_waves)
     bounds = max(len(schedule[0][0]), 4) if schedule else "WG_MAX_WAVES"
     return "\n".join([
@@ -221,11 +221,12 @@ def _version_tag() -> str:
 
 
 def _headers_digest() -> str:
+    """Every header a plan unit can include: all of csrc/*.h and include/*.h, names sorted."""
     h = hashlib.sha256()
-    for p in (os.path.join(CSRC, "vbn_walk_impl.h"), os.path.join(CSRC, "vbn_walk_plan.h"),
-              os.path.join(INCLUDE, "vbn_hip.h"), os.path.join(INCLUDE, "vbn_hip_types.h")):
-        with open(p, "rb") as f:
-            h.update(f.read())
+    for d in (CSRC, INCLUDE):
+        for name in sorted(n for n in os.listdir(d) if n.endswith(".h")):
+            with open(os.path.join(d, name), "rb") as f:
+                h.update(f.read())
     return h.hexdigest()[:16]
 
 

@@ -22,7 +22,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .plan import MODE_GIBBS, MODE_MCM, S_WBLK_LEN, STEP_INTS
+from .plan import KM_NOISELESS, KM_TABLE, MODE_GIBBS, MODE_MCM, S_WBLK_LEN, STEP_INTS
 
 __all__ = ["walk", "walk_segment", "table_walk", "normalize_weights", "rb_epilogue", "resample", "posterior_stats"]
 
@@ -183,7 +183,7 @@ def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_sam
     a.dmax = dmax
     a.n_out_cols = n_out_cols
     a.mode = mode
-    a.kind_mask = 1024
+    a.kind_mask = KM_TABLE
     a.q_base = q_base
     a.seed = seed & ((1 << 64) - 1)
     a.offset = offset & ((1 << 64) - 1)
@@ -343,7 +343,7 @@ def _plan_module(lib, a, steps, step_begin, step_end, work, plan_jit, device, ch
     if km <= 0:
         return None
     if a.mode == MODE_GIBBS and not a.noise:
-        km |= 256           # the draw-free unit at full wave too (vbn_hip_walk_module)
+        km |= KM_NOISELESS  # the draw-free unit at full wave too (vbn_hip_walk_module)
     # auto: a compiled plan serves every launch size (bit-identical outputs, so the choice never
     # depends on how a batch is sharded); large launches start a missing compile in the background
     compile = "sync" if plan_jit == 2 else ("background" if work >= jit.JIT_MIN_PARTICLES else "never")
@@ -875,7 +875,7 @@ def _query_walk(plan, params, fixed, n_samples, seed, offset, q_base, noise, pla
     secs = _unpack(plan, device)
     if secs[0] is None:
         raise ValueError("vbn_hip: plan has no walk section")
-    if int(secs[0][3][8]) & 1024:
+    if int(secs[0][3][8]) & KM_TABLE:
         raise NotImplementedError("vbn_hip: the query-level ops are not implemented for categorical_table plans "
                                   "(use the engines, which run them on vbn_hip::table_walk)")
     b = int(fixed.shape[0])

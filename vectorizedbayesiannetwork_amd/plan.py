@@ -6,7 +6,7 @@ slices, evidence/do masks) and re-reads CPD parameters inside every ATen call.  
 work is split in two device-resident objects:
 
 * :class:`PackedModel` — once per model and device: every CPD's parameters packed into one
-  fp32 blob in the fragment layouts the kernel reads (see ``csrc/vbn_walk_impl.h``), plus the
+  fp32 blob in the fragment layouts the kernel reads (see ``csrc/vbn_walk_mlp.h``), plus the
   host-side constants the reference recomputes per call (root loc/scale, mixture weights,
   KDE kernel scales), computed with the same torch fp32 ops so they are bit-identical.
 * :class:`QueryPlan` — once per (query signature, engine mode): the ``vbn_step`` table
@@ -28,9 +28,18 @@ import torch.nn.functional as F
 
 from .model import BNModel, CPDRecord
 
-# ---- must match include/vbn_hip.h -------------------------------------------------------
+# ---- the values of include/vbn_hip_types.h and csrc/*.h (tests/test_layout_constants.py compares) ----
 KIND_ID = {"gaussian_nn": 0, "linear_gaussian": 1, "mdn": 2, "kde": 3, "softmax_nn": 4, "categorical_table": 5}
-KIND_MASK_TABLE = 1024    # kind_mask of a plan whose walked steps are all categorical_table (bit 5 = non-relu)
+# kind-set bits (VBN_KM_*): bits 0-4 = 1 << kind of every CPD kind walked, then
+KM_NONRELU = 32           # some NN CPD has a non-relu activation
+KM_HALFWAVE = 64          # half-wave launch (wave_particles 32)
+KM_LEAN = 128             # no injected draws, no segment state, not Gibbs
+KM_NOISELESS = 256        # no injected draws (production Gibbs sweeps)
+KM_GENERIC_MLP = 512      # some NN CPD has hidden_dims other than (32, 32)
+KM_TABLE = 1024           # kind_mask of a plan whose walked steps are all categorical_table
+KM_KINDS = 63             # the plan's CPD kinds and KM_NONRELU
+KM_NN_KINDS = 21          # any NN kind: gaussian_nn | mdn | softmax_nn
+KM_UNSTAGED_KINDS = 28    # mdn | kde | softmax_nn: kind sets that read weights from the blob, not LDS
 ROLE_SKIP, ROLE_LATENT, ROLE_FIXED, ROLE_PARAMS, ROLE_SELECT, ROLE_COLLECT = 0, 1, 2, 3, 4, 5
 F_LOGP, F_ROOT, F_SHARED, F_STANDARDIZE, F_CLIP, F_F32L2, F_KDE_VALU = 1, 2, 4, 8, 16, 32, 64
 F_KEEP, F_LPRESET, F_BM_FIRST, F_BM_SECOND, F_MLP_GENERIC = 128, 256, 512, 1024, 2048
@@ -41,7 +50,11 @@ STEP_INTS = 32
 (S_KIND, S_ROLE, S_FLAGS, S_ACT, S_NIN, S_INOFF, S_OUTCOL, S_OUTDIM, S_FIXEDCOL, S_K, S_NOUT,
  S_NODEID, S_NOISE, S_AUX0, S_AUX1, S_AUX2, S_OFF_STD, S_OFF_W1, S_OFF_W2, S_OFF_B2, S_OFF_W3,
  S_OFF_B3, S_OFF_TAIL, S_OFF_PTS, S_OFF_W2H, S_OFF_KQ, S_OFF_KQY, S_OFF_KR, S_OFF_KV,
- S_WBLK_OFF, S_WBLK_LEN, S_RES7) = range(32)
+ S_WBLK_OFF, S_WBLK_LEN, S_OFF_KMT) = range(32)
+# the words that mean something else on another step kind (csrc step_zlim, step_off_w3h, step_off_kmt2)
+S_ZLIM = S_OFF_KQ         # NN steps: f32 bits of the layer-1 operand bound
+S_OFF_W3H = S_OFF_KQY     # NN steps with F_HEAD_MFMA: split-f16 head fragments
+S_OFF_KMT2 = S_OFF_W1     # kde steps: two-feature moment table, -1 = none
 WBLK_CHUNK = 256          # floats per LDS-DMA wave instruction (64 lanes x 16 B)
 KDE_CHUNKS = 16
 KDE_REC_TAIL = 16      # weight-0 record rows after the last point (csrc kde_scan: two trips of 4 ahead)
@@ -97,7 +110,7 @@ def _kde_cb(m: int) -> int:
 
 
 def _kde_pack(feats: List[np.ndarray], records: bool = False) -> np.ndarray:
-    """KDE point features y' (scaled) for the kernel (csrc/vbn_walk_impl.h, kde_mfma_sums).
+    """KDE point features y' (scaled) for the kernel (csrc/vbn_walk_kde.h, kde_mfma_sums).
 
     MFMA A-operand image: [KDE_CHUNKS * cb][4][16] fp32 (cb = _kde_cb(M) blocks per chunk),
     columns (y'_0 .. y'_{nf-1}, |y'|^2, 1) for nf <= 2 and (y'_0, y'_1, y'_2, |y'|^2) for
@@ -451,7 +464,7 @@ def _pack_mlp_generic(blob: _Blob, layers, offs: Dict[str, int]) -> Dict[str, in
 
 
 def _pack_mlp(blob: _Blob, rec: CPDRecord, standardize: bool) -> Dict[str, int]:
-    """MFMA fragment layouts of csrc/vbn_walk_impl.h mlp_forward (biases as accumulator init);
+    """MFMA fragment layouts of csrc/vbn_walk_mlp.h mlp_forward (biases as accumulator init);
     other hidden_dims than (32, 32) get the generic layer-by-layer pack (mlp_generic)."""
     layers = rec.mlp_layers()
     hidden = tuple(int(w.shape[0]) for w, _ in layers[:-1])
@@ -676,7 +689,7 @@ def _pack_node(blob: _Blob, rec: CPDRecord) -> NodePack:
         c_y = np.float32(_KDE_C / s_y)
         offs["tail"] = blob.add(np.array([1.0 / np.float32(s_p), 1.0 / np.float32(s_y),
                                           noise_scale, cy, math.log(float(m)), c_p, c_y, 0], np.float32))
-        # MFMA packs (csrc/vbn_walk_impl.h, kde_b32_sums): bf16x3 point slots, [block][g][h][32][8]
+        # MFMA packs (csrc/vbn_walk_kde.h, kde_b32_sums): bf16x3 point slots, [block][g][h][32][8]
         if 1 <= dp <= 3:
             offs["kq"] = blob.add(_kde_pack_b32(_np(pts_p) * c_p))
             offs["kr"] = blob.add(_kde_pack([_np(pts_p) * c_p], records=True))
@@ -787,7 +800,7 @@ class QueryPlan:
     mode: int
     slot_of: Dict[str, int]
     kind_mask: int = 63       # CPD kinds the walk evaluates (selects the kernel instantiation;
-                              # | 32 non-relu activations, | 512 generic-MLP nodes)
+                              # | KM_NONRELU, | KM_GENERIC_MLP)
     order: Optional[List[str]] = None   # the walk order of the steps (a topological order)
     wbuf: int = 0             # floats per LDS weight buffer (max wblk_len over the steps)
     # precompute (precompute_plans): the same walk with VBN_F_PRECOMP steps, the one-query
@@ -994,6 +1007,8 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
             fl |= F_PRE_OUT
         if n in clamp_s and n in fixed_s:
             fl |= F_CLAMP_EV
+        if "w3h" in npk.offs:
+            fl |= F_HEAD_MFMA
         row[S_FLAGS] = fl
         row[S_ACT] = npk.act
         row[S_NIN] = npk.n_in
@@ -1010,23 +1025,24 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
         row[S_NOISE] = noise_idx.get(n, 0)
         row[S_AUX0] = npk.aux0
         row[S_AUX1] = npk.aux1
-        for key, idx in (("std", S_OFF_STD), ("w1", S_OFF_W1), ("w2", S_OFF_W2), ("b2", S_OFF_B2),
-                         ("w3", S_OFF_W3), ("b3", S_OFF_B3), ("tail", S_OFF_TAIL), ("pts", S_OFF_PTS),
-                         ("w2h", S_OFF_W2H)):
+        for key, idx in (("std", S_OFF_STD), ("w2", S_OFF_W2), ("b2", S_OFF_B2), ("w3", S_OFF_W3),
+                         ("b3", S_OFF_B3), ("tail", S_OFF_TAIL), ("pts", S_OFF_PTS), ("w2h", S_OFF_W2H)):
             row[idx] = npk.offs.get(key, 0)
-        row[S_OFF_KQ] = npk.offs.get("kq", -1)
-        if "zlim" in npk.offs:                   # NN steps: layer-1 operand bound (f32 bits)
-            row[S_OFF_KQ] = np.float32(npk.offs["zlim"]).view(np.int32)
-        row[S_OFF_KQY] = npk.offs.get("kqy", -1)
+        if npk.kind == KIND_ID["kde"]:           # moment table of a two-feature node
+            row[S_OFF_KMT2] = npk.offs.get("kmt2", -1)
+        else:
+            row[S_OFF_W1] = npk.offs.get("w1", 0)
+        if "zlim" in npk.offs:                   # NN steps: layer-1 operand bound
+            row[S_ZLIM] = np.float32(npk.offs["zlim"]).view(np.int32)
+        else:
+            row[S_OFF_KQ] = npk.offs.get("kq", -1)
         if "w3h" in npk.offs:                    # NN steps: split-f16 head fragments
-            row[S_OFF_KQY] = npk.offs["w3h"]
-            fl |= F_HEAD_MFMA
-            row[S_FLAGS] = fl
+            row[S_OFF_W3H] = npk.offs["w3h"]
+        else:
+            row[S_OFF_KQY] = npk.offs.get("kqy", -1)
         row[S_OFF_KR] = npk.offs.get("kr", -1)
         row[S_OFF_KV] = npk.offs.get("kv", -1)
-        row[S_RES7] = npk.offs.get("kmt", -1)   # kde: moment table of a one-feature node
-        if npk.kind == KIND_ID["kde"]:          # kde: 2-D moment table of a two-feature node (off_w1
-            row[S_OFF_W1] = npk.offs.get("kmt2", -1)      # is an NN field: -1 = none on kde steps)
+        row[S_OFF_KMT] = npk.offs.get("kmt", -1)   # kde: moment table of a one-feature node
         if "wblk" in npk.offs and (n in latent_s or n in logp_s or n in params_s):
             row[S_WBLK_OFF] = npk.offs["wblk"]
             row[S_WBLK_LEN] = npk.offs["wblk_len"]
@@ -1046,13 +1062,13 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
             npk = packed.nodes[n]
             kind_mask |= 1 << npk.kind
             if npk.n_out and npk.act != ACT_ID["relu"]:
-                kind_mask |= 32
+                kind_mask |= KM_NONRELU
             if npk.flags & F_MLP_GENERIC:
-                kind_mask |= 512                 # csrc kind-set bit 9: the generic-MLP path
+                kind_mask |= KM_GENERIC_MLP
     tabular = bool(getattr(packed, "tabular", False))
     wbuf = int(steps[:, S_WBLK_LEN].max()) if len(order) else 0
     if tabular:
-        kind_mask = KIND_MASK_TABLE
+        kind_mask = KM_TABLE
         wbuf = int(packed.params.numel())
         # the table walk keeps class indices in the slots: per output column, where its class
         # values are in the blob (-1: a PARAMS column, the slot holds the probability itself)
@@ -1502,7 +1518,7 @@ def precompute_plans(packed: PackedModel, plan: QueryPlan, *, skip: Sequence[str
         # a KDE node with a moment table computes its chunk sums from the table in a few FMAs;
         # precomputing them would only force the pre-pass's 16 coarse chunks on its scan
         return (kind == KIND_ID["kde"] and role == ROLE_LATENT and not r[S_FLAGS] & F_KDE_VALU
-                and r[S_OFF_KQ] >= 0 and r[S_RES7] < 0)
+                and r[S_OFF_KQ] >= 0 and r[S_OFF_KMT] < 0)
 
     cand_s = [n for n in order if qualifies(n) and all(p in root_s for p in model.parents[n])]
     cand_q = [n for n in order if per_query and qualifies(n) and all(p in fixed_s for p in model.parents[n])]
