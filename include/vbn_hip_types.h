@@ -22,7 +22,9 @@ enum vbn_kind {
   VBN_KIND_MDN = 2,
   VBN_KIND_KDE = 3,
   VBN_KIND_SOFTMAX_NN = 4,
-  VBN_KIND_CATEGORICAL_TABLE = 5  /* walked by vbn_hip_table_walk only (csrc/vbn_table_walk.hip) */
+  VBN_KIND_CATEGORICAL_TABLE = 5, /* walked by vbn_hip_table_walk only (csrc/vbn_table_walk.hip) */
+  VBN_KIND_RFF_GAUSSIAN = 6       /* random Fourier feature regressor (csrc/vbn_walk_rff.h); its plans
+                                     set VBN_KM_GENERIC_MLP, not a kind bit of their own */
 };
 
 /* role of a node for one query signature */
@@ -32,7 +34,7 @@ enum vbn_role {
   VBN_ROLE_FIXED = 2,
   VBN_ROLE_PARAMS = 3,  /* write the CPD's conditional parameters, no draw (RB target,
                            CPDHandle.conditional, vbn/core/cpd_handle.py:40-118):
-                           gaussian_nn / linear_gaussian: loc[D] ++ scale[D];
+                           gaussian_nn / linear_gaussian / rff_gaussian: loc[D] ++ scale[D];
                            softmax_nn / categorical_table: class probabilities[D][C];
                            mdn: softmax(logits)[K] ++ loc[K][D] ++ scale[K][D]           */
   VBN_ROLE_SELECT = 4,  /* Gibbs: softmax over the 8 candidate lanes of a chain, choose one,
@@ -95,12 +97,14 @@ enum vbn_mode {
 
 /* Kind-set bits: which walk instantiation runs a plan (vbn_walk_args.kind_mask holds the plan's
  * part, the launcher adds the launch form; csrc/vbn_walk_kernel.h VBN_WALK_KIND_SETS lists the
- * instantiated sets).  Bits 0-4 = 1 << vbn_kind of every CPD kind walked. */
+ * instantiated sets).  Bits 0-4 = 1 << vbn_kind of every CPD kind walked (kinds 0-4; rff_gaussian
+ * sets VBN_KM_GENERIC_MLP instead). */
 #define VBN_KM_NONRELU 32        /* some NN CPD has a non-relu activation                      */
 #define VBN_KM_HALFWAVE 64       /* half-wave (mirror) launch, wave_particles = 32             */
 #define VBN_KM_LEAN 128          /* no injected draws, no segment state, not Gibbs             */
 #define VBN_KM_NOISELESS 256     /* no injected draws (production Gibbs sweeps)                */
-#define VBN_KM_GENERIC_MLP 512   /* some NN CPD has hidden_dims other than (32, 32)            */
+#define VBN_KM_GENERIC_MLP 512   /* some step runs out of line: an NN CPD with hidden_dims other
+                                    than (32, 32) (mlp_generic) or an rff_gaussian node           */
 #define VBN_KM_TABLE 1024        /* alone: every step is a categorical_table (vbn_hip_table_walk) */
 #define VBN_KM_KINDS 63          /* the plan's CPD kinds and VBN_KM_NONRELU                    */
 #define VBN_KM_NN_KINDS 21       /* any NN kind: gaussian_nn | mdn | softmax_nn                */
@@ -166,7 +170,7 @@ typedef struct vbn_walk_args {
   int32_t dmax;
   int32_t n_out_cols;
   int32_t mode;            /* enum vbn_mode                                        */
-  int32_t kind_mask;       /* CPD kinds walked: 1<<kind, | VBN_KM_NONRELU, | VBN_KM_GENERIC_MLP;
+  int32_t kind_mask;       /* CPD kinds walked: 1<<kind (kinds 0-4), | VBN_KM_NONRELU, | VBN_KM_GENERIC_MLP;
                               VBN_KM_TABLE alone: every step is a categorical_table
                               (vbn_hip_table_walk; vbn_hip_walk refuses it)             */
   int64_t q_base;          /* global index of query 0 (multi-GPU shards)            */

@@ -60,10 +60,36 @@ def plans_for(name):
     return cfg, out
 
 
+RFF8 = "rff8"          # the rff_gaussian fixture's walks (tests/test_gpu_rff.py), not a bench config
+
+
+def rff8_plans():
+    """The two every-node-out walks of tests/golden/rff/rff8.pt that tests/test_gpu_rff.py also runs
+    plan-specialised, with injected draws: the full-wave kind set with the out-of-line steps (bit 9)
+    and every kind, which is what vbn_hip_walk_kind_set gives such a launch."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import rff_reference as R
+    from vectorizedbayesiannetwork_amd import jit
+    from vectorizedbayesiannetwork_amd import plan as P
+    from vectorizedbayesiannetwork_amd.model import model_from_checkpoint
+    fx = R.load_rff8()
+    pk = P.PackedModel(model_from_checkpoint(fx["model"]), "cpu")
+    lines = []
+    for case, weighted in R.jit_walk_cases(fx):
+        plan = R.all_nodes_plan(pk, case, weighted)
+        assert plan.kind_mask & P.KM_GENERIC_MLP
+        steps, ic, _ = plan.steps._vbn_host
+        t0, c0 = time.perf_counter(), jit.STATS["compile_s"]
+        key, _ = jit.code_object(steps, ic, P.KM_GENERIC_MLP | P.KM_KINDS)
+        lines.append(f"{RFF8} {'weighted' if weighted else 'sample'}: {key} "
+                     f"({'compiled' if jit.STATS['compile_s'] > c0 else 'cached'} in {time.perf_counter() - t0:.1f} s)")
+    return lines
+
+
 BENCH = ["cfg2", "cfg3", "cfg4", "cfg5", "anchor64"]
 # the extra plans of the GPU tests' workloads
 TESTS = ["cfg2:is", "cfg2:lw", "cfg3:lw", "cfg3:mcm", "cfg3:ancestral", "cfg4:lw", "cfg4:ancestral",
-         "cfg5:lw", "cfg5:ancestral"]
+         "cfg5:lw", "cfg5:ancestral", RFF8]
 TAGS = ("plain", "precompute")
 
 
@@ -72,6 +98,8 @@ def _one(task):
     gives no line."""
     from vectorizedbayesiannetwork_amd import jit
     name, want = task
+    if name == RFF8:
+        return rff8_plans() if want == TAGS[0] else []
     cfg, plans = plans_for(name)
     lines = []
     for tag, plan, pre in plans:
@@ -91,12 +119,14 @@ def main(names):
         expanded += BENCH if name == "--bench" else TESTS if name == "--tests" else [name]
     names = list(dict.fromkeys(expanded))
     for name in names:
+        if name == RFF8:
+            continue
         if name.partition(":")[0] not in synthetic.CONFIGS or name.partition(":")[2] not in ("", *ENGINES):
             raise SystemExit(f"unknown config {name}")
     # one task per plan, not per workload (a 128-node plan compiles for minutes, and a workload's
     # two plans need not wait for each other), the workloads with most nodes first; one hiprtc
     # compile per process at a time (single-threaded, ~1-2 GB each)
-    names.sort(key=lambda n: -synthetic.CONFIGS[n.partition(":")[0]]["n_nodes"])
+    names.sort(key=lambda n: -(8 if n == RFF8 else synthetic.CONFIGS[n.partition(":")[0]]["n_nodes"]))
     tasks = [(name, tag) for name in names for tag in TAGS]
     workers = max(1, min(len(tasks), (os.cpu_count() or 1), 8))
     with ProcessPoolExecutor(workers) as ex:

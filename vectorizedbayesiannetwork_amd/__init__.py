@@ -1,5 +1,6 @@
 """MI355X-native batched Bayesian-network inference (drop-in for VBN's MCM / IS / LW / RB /
-RIS / ancestral path and the gaussian_nn / linear_gaussian / mdn / kde / softmax_nn CPDs, and
+RIS / gaussian_exact / ancestral path and the gaussian_nn / linear_gaussian / rff_gaussian / mdn / kde /
+softmax_nn CPDs, and
 for MCM / IS / LW / ancestral / categorical_exact on all-categorical_table networks).
 
 Importing the package does not touch the GPU; the HIP library is loaded on first use and
@@ -9,6 +10,7 @@ from .registry import INFERENCE_REGISTRY, SAMPLING_REGISTRY  # noqa: F401
 from .engines import (  # noqa: F401
     AncestralSampler,
     CategoricalExact,
+    GaussianExact,
     ImportanceSampling,
     LikelihoodWeighting,
     MonteCarloMarginalization,

@@ -44,6 +44,7 @@ _ENGINE_DEFAULTS = {
         "resampled_importance_sampling": {"n_samples": 1024, "ess_threshold": 0.5, "resample": True,
                                           "clamp_obs": True},
         "categorical_exact": {"fallback": "likelihood_weighting"},
+        "gaussian_exact": {"n_samples": 512, "stddevs": 4.0, "min_scale": 1e-6, "fallback": "likelihood_weighting"},
     },
     "sampling": {"ancestral": {"n_samples": 512},
                  "gibbs": {"n_samples": 512, "burn_in": 50, "n_steps": 5}},

@@ -89,7 +89,7 @@ def cpd_forward(vbn, node: str, parents: Optional[torch.Tensor], n_samples: int,
 
 def cpd_params(vbn, node: str, parents: Optional[torch.Tensor], n_rows: int = 1) -> torch.Tensor:
     """The node's conditional parameters per parent row (walk role PARAMS): ``[B, n_rows, W]``
-    with gaussian_nn / linear_gaussian ``loc[D] ++ scale[D]``, softmax_nn class
+    with gaussian_nn / linear_gaussian / rff_gaussian ``loc[D] ++ scale[D]``, softmax_nn class
     probabilities ``[D][C]``, mdn ``softmax(logits)[K] ++ loc[K][D] ++ scale[K][D]``.
     ``parents``: [B, d] (n_rows = 1), [B, n_rows, d], or None for a root (B = 1)."""
     dev = _device_of(vbn)

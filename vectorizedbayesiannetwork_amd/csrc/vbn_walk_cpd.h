@@ -1,7 +1,9 @@
 #pragma once
 // vbn_walk_cpd.h -- the parametric CPD steps: gaussian_nn, linear_gaussian, mdn, softmax_nn and
-// their inverse-CDF search (part of vbn_walk_impl.h).
+// their inverse-CDF search; rff_gaussian has a header of its own, included here (part of
+// vbn_walk_impl.h).
 #include "vbn_walk_mlp.h"
+#include "vbn_walk_rff.h"
 
 // value of node dim d for this particle: fresh draw result or fixed input
 #define NODE_X(d) (vread(L, st.out_col + (d)))

@@ -47,8 +47,8 @@ __device__ __forceinline__ void gibbs_collect(const vbn_walk_args& A, const vbn_
 // ------------------------------------------------------------------------------------------
 // One step of the walk for the wave's 64 particles.
 // KM: bit0 gaussian_nn, bit1 linear_gaussian, bit2 mdn, bit3 kde, bit4 softmax_nn,
-// bit5 non-relu activations.  Each instantiation only carries the code (and registers) of
-// the CPD kinds a plan uses.
+// bit5 non-relu activations, bit9 the out-of-line steps (generic MLPs, rff_gaussian).  Each
+// instantiation only carries the code (and registers) of the CPD kinds a plan uses.
 template <unsigned KM>
 __device__ __forceinline__ void walk_step(const vbn_walk_args& A, const vbn_step& st, Lane& L, float& lp) {
   if (st.role == VBN_ROLE_SKIP) return;
@@ -75,6 +75,16 @@ __device__ __forceinline__ void walk_step(const vbn_walk_args& A, const vbn_step
     for (int d = 0; d < st.out_dim; ++d) vwrite(L, st.out_col + d, node_fixed(A, st, d, L));
     wave_sync();
     return;
+  }
+  // rff_gaussian runs out of line in the kind sets with bit 9 only (its plans set the bit, as
+  // generic-MLP plans do).  It is tested here and not as a case of the switch below, whose
+  // default is softmax_nn: a sixth case changed the code of every other instantiation
+  if constexpr ((KM & VBN_KM_GENERIC_MLP) != 0) {
+    if (st.kind == VBN_KIND_RFF_GAUSSIAN) {
+      step_rff_gaussian<KM>(A, st, L, lp);
+      wave_sync();
+      return;
+    }
   }
   switch (st.kind) {
     case VBN_KIND_GAUSSIAN_NN: if constexpr ((KM & 1) != 0) step_gaussian_nn<KM>(A, st, L, lp); break;
@@ -270,9 +280,10 @@ vbn_walk_kernel(const vbn_walk_args A, const float* __restrict__ params, const v
 // half-wave (mirror) launch (include/vbn_hip.h wave_particles = 32), bit 7 the lean walk (no
 // injected draws, no segment state, not Gibbs: the production MCM / IS / LW / ancestral path;
 // measured cfg2 1.215 -> 1.19 ms, SGPR spills 35 -> 0), bit 8 no injected draws (with bit 6: the
-// production half-wave Gibbs sweeps; SGPR spills 34 -> 9), bit 9 the generic-MLP path (plans
-// with hidden_dims other than (32, 32): only with the all-kinds set 63, so the out-of-line
-// mlp_generic call never touches the hot instantiations' registers).  Each is compiled in its
+// production half-wave Gibbs sweeps; SGPR spills 34 -> 9), bit 9 the out-of-line steps (plans
+// with an NN CPD of hidden_dims other than (32, 32) or with an rff_gaussian node: only with the
+// all-kinds set 63, so the out-of-line mlp_generic / rff_loc calls never touch the hot
+// instantiations' registers).  Each is compiled in its
 // own object from walk_inst.hip (Makefile KIND_SETS must list the same values).
 #define VBN_WALK_KIND_SETS(X) \
   X(1) X(2) X(3) X(4) X(8) X(16) X(20) X(23) X(31) X(63) \

@@ -34,6 +34,7 @@ For parity tests the draws can be injected (``_noise=``).
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 import threading
 from dataclasses import dataclass, field
@@ -762,6 +763,11 @@ class ImportanceSampling(LikelihoodWeighting):
         return w, xs
 
 
+# kinds whose conditional is one normal per output dim (PARAMS: loc ++ scale): the reference
+# reaches them through its ``_weight`` (linear_gaussian) and ``_params`` branches
+_GAUSSIAN_KINDS = ("gaussian_nn", "linear_gaussian", "rff_gaussian")
+
+
 def _descendants(model: BNModel, node: str) -> set:
     ch = model.children()
     out, stack = set(), [node]
@@ -831,7 +837,7 @@ class RaoBlackwellizedMarginalization(_EngineBase):
         rec = model.cpds[target]
         if rec.kind == "softmax_nn" and model.out_dim(target) == 1:
             mode = 1
-        elif rec.kind in ("gaussian_nn", "linear_gaussian") and model.out_dim(target) == 1:
+        elif rec.kind in _GAUSSIAN_KINDS and model.out_dim(target) == 1:
             mode = 0
         else:
             return self._fallback_infer(vbn, query, reason="unsupported target CPD for RB marginalization",
@@ -906,6 +912,73 @@ class CategoricalExact:
         _, probs = run_walk(pk, plan, fx, b, 1, seed=0, q_base=self.q_base)
         support = rec.state["_sample_values"][0].to(device=dev, dtype=torch.float32)   # 81-82
         return probs.view(b, -1), support.view(1, -1, 1).expand(b, -1, 1)
+
+
+@register_inference("gaussian_exact")
+class GaussianExact:
+    """gaussian_exact.py:14-183 on the GPU: the exact density of a one-dimensional Gaussian target
+    (linear_gaussian, gaussian_nn, rff_gaussian) whose parents are all observed, on a fixed grid of
+    ``n_samples`` points over +- ``stddevs`` standard deviations (a PARAMS walk at S = 1 over the
+    target and its parents, then O(B n) torch ops on the device); the configured fallback engine
+    for every other query.  mdn and softmax_nn targets are excluded by the reference's
+    ``n_components`` / ``n_classes`` test, kde has neither ``_weight`` nor ``_params``."""
+
+    def __init__(self, n_samples: int = 200, stddevs: float = 4.0, min_scale: float = 1e-6,
+                 fallback: Optional[str] = "likelihood_weighting", **kwargs):
+        self.n_samples = int(n_samples)
+        self.stddevs = float(stddevs)
+        self.min_scale = float(min_scale)
+        self.fallback = str(fallback).strip().lower() if fallback is not None else "none"
+        self._fallback = None
+        self._last_fallback = False
+        self.q_base = int(kwargs.get("q_base", 0))
+        if self.fallback != "none":
+            from .registry import INFERENCE_REGISTRY
+            if self.fallback not in INFERENCE_REGISTRY:
+                raise ValueError(
+                    f"Unknown fallback inference '{fallback}'. Available: {list(INFERENCE_REGISTRY.keys())}")
+            if self.fallback == "gaussian_exact":
+                raise ValueError("fallback cannot be 'gaussian_exact'")
+            fk = dict(kwargs)
+            fk.setdefault("n_samples", self.n_samples)
+            self._fallback = INFERENCE_REGISTRY[self.fallback](**fk)
+
+    def _fallback_infer(self, vbn, query, **kwargs):
+        self._last_fallback = True
+        if self._fallback is None:
+            raise RuntimeError("gaussian_exact cannot handle this query and has no fallback")
+        return self._fallback.infer_posterior(vbn, query, **kwargs)
+
+    def infer_posterior(self, vbn, query, **kwargs):
+        self._last_fallback = False
+        n = max(1, int(kwargs.get("n_samples", self.n_samples)))                      # 135
+        target, ev, do = _EngineBase._query(query)
+        b = infer_batch_size(ev, do)
+        dev = _device_of(vbn)
+        pk = packed_model(vbn, dev)
+        model = pk.model
+        if model.out_dim(target) != 1:                                                # 146-147
+            return self._fallback_infer(vbn, query, **kwargs)
+        vals = _fixed_values(query, dev, clamp=True)                                  # 141: clamp_obs
+        if target in vals:                                                            # 149-153
+            return (torch.ones(b, 1, device=dev, dtype=torch.float32),
+                    vals[target].unsqueeze(1).expand(b, 1, -1))
+        parents = model.parents[target]
+        if not all(p in vals for p in parents) or model.cpds[target].kind not in _GAUSSIAN_KINDS:   # 155-170
+            return self._fallback_infer(vbn, query, **kwargs)
+        nodes = set(parents) | {target}
+        plan = _plan(pk, ("gauss-exact", target), latent=[], fixed=[x for x in model.topo if x in parents], logp=[],
+                     out_nodes=[target], params=[target], shared_roots=True, mode=MODE_SAMPLE,
+                     skip=[x for x in model.topo if x not in nodes])
+        fx = _fixed_buffer(plan, vals, b, dev)
+        _, prm = run_walk(pk, plan, fx, b, 1, seed=0, q_base=self.q_base)           # [B, 1, loc ++ scale]
+        loc, scale = prm[..., :1], prm[..., 1:2]
+        ms = self.min_scale
+        scale = torch.nan_to_num(scale, nan=ms, posinf=ms, neginf=ms).abs().clamp_min(ms)          # 128-131
+        z = torch.linspace(-self.stddevs, self.stddevs, n, device=dev, dtype=torch.float32).view(1, n, 1)
+        samples = loc + scale * z                                                     # 177
+        log_pdf = -0.5 * (z ** 2 + 2.0 * torch.log(scale) + math.log(2.0 * math.pi)).sum(dim=-1)
+        return torch.exp(log_pdf), samples
 
 
 @register_inference("resampled_importance_sampling")

@@ -5,7 +5,7 @@
 ``pdf`` / ``forward`` run the node's CPD on the MI355X (:mod:`.cpd`); ``conditional`` returns
 the reference's formats (``cpd_handle.py:348-404``):
 
-* ``normal_params``   -- gaussian_nn, linear_gaussian: ``mean`` / ``std`` [B, 1 | S, D]
+* ``normal_params``   -- gaussian_nn, linear_gaussian, rff_gaussian: ``mean`` / ``std`` [B, 1 | S, D]
   (walk role PARAMS);
 * ``mixture_params``  -- mdn: ``weights`` = softmax(logits) [B, 1, K], ``loc`` / ``scale``
   [B, 1, K, D] (PARAMS);
@@ -29,7 +29,10 @@ from .model import CPDRecord
 __all__ = ["CPDHandle", "to_serializable"]
 
 _CLASS_NAME = {"gaussian_nn": "GaussianNNCPD", "linear_gaussian": "LinearGaussianCPD", "mdn": "MDNCPD",
-               "kde": "KDECPD", "softmax_nn": "SoftmaxNNCPD", "categorical_table": "CategoricalTableCPD"}
+               "kde": "KDECPD", "softmax_nn": "SoftmaxNNCPD", "categorical_table": "CategoricalTableCPD",
+               "rff_gaussian": "RFFGaussianCPD"}
+# kinds whose conditional is one normal per output dim (PARAMS: loc ++ scale)
+_NORMAL_KINDS = ("gaussian_nn", "linear_gaussian", "rff_gaussian")
 
 
 def to_serializable(obj, *, max_tensor_elems: int = 2048):
@@ -204,7 +207,7 @@ class CPDHandle:
                     "std": s.std(dim=1, unbiased=False), "n_samples": int(n_samples)}
         prm = C.cpd_params(self._vbn, self._node, pt)                  # [B, 1 | S, W]
         b, s = prm.shape[0], prm.shape[1]
-        if kind in ("gaussian_nn", "linear_gaussian"):
+        if kind in _NORMAL_KINDS:
             return {"format": "normal_params", "mean": prm[..., :D], "std": prm[..., D:2 * D]}
         if kind == "mdn":
             k = int(self._rec.hp("n_components"))
@@ -230,7 +233,7 @@ class CPDHandle:
 
     def conditional_mean_std(self, parents, n_samples: int = 1024) -> dict:
         """reference cpd_handle.py:415-428"""
-        if self._rec.kind in ("gaussian_nn", "linear_gaussian"):
+        if self._rec.kind in _NORMAL_KINDS:
             t = self.conditional_tensors(parents)
             return {"format": "normal_params", "mean": t["mean"], "std": t["std"]}
         s = self.sample(parents, n_samples)

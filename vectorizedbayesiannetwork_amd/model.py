@@ -40,7 +40,7 @@ __all__ = [
 ]
 
 # Registry keys of the reference CPDs on the hot path (reference core/registry.py + cpds/*).
-CPD_KINDS = ("gaussian_nn", "linear_gaussian", "mdn", "kde", "softmax_nn", "categorical_table")
+CPD_KINDS = ("gaussian_nn", "linear_gaussian", "mdn", "kde", "softmax_nn", "categorical_table", "rff_gaussian")
 
 _CLASS_TO_KIND = {
     "GaussianNNCPD": "gaussian_nn",
@@ -49,10 +49,11 @@ _CLASS_TO_KIND = {
     "KDECPD": "kde",
     "SoftmaxNNCPD": "softmax_nn",
     "CategoricalTableCPD": "categorical_table",
+    "RFFGaussianCPD": "rff_gaussian",
 }
 
 # Constructor defaults of the reference classes (gaussian_nn.py:41-50, linear_gaussian.py:14-22,
-# mdn.py:41-51, kde.py:17-27, softmax_nn.py:52-71, categorical_table.py:27-38).  Values that a checkpoint carries in
+# mdn.py:41-51, kde.py:17-27, softmax_nn.py:52-71, categorical_table.py:27-38, rff_gaussian.py:17-28).  Values that a checkpoint carries in
 # ``init_kwargs`` override these.
 KIND_DEFAULTS: Dict[str, Dict[str, Any]] = {
     "gaussian_nn": dict(hidden_dims=(32, 32), activation="relu", min_scale=1e-3),
@@ -65,6 +66,7 @@ KIND_DEFAULTS: Dict[str, Dict[str, Any]] = {
                        mode_when_not_discrete="binned"),
     "categorical_table": dict(n_classes=0, parent_n_classes=None, alpha=1.0, alpha_mode="per_class",
                               prior="uniform"),
+    "rff_gaussian": dict(n_features=256, lengthscale=1.0, ridge=1e-6, min_scale=1e-3, use_bias=True),
 }
 
 # The packaged YAML defaults the reference's ``defaults.cpd(kind)`` returns
@@ -77,6 +79,7 @@ YAML_DEFAULTS: Dict[str, Dict[str, Any]] = {
     "softmax_nn": dict(n_classes=8, hidden_dims=(32, 32), activation="relu",
                        min_bin_width=1e-12, binning="quantile", within_bin="triangular"),
     "categorical_table": dict(n_classes=0, alpha=1.0, alpha_mode="total_mass", prior="global"),
+    "rff_gaussian": dict(n_features=256, lengthscale=1.0, ridge=1e-6, min_scale=1e-3, use_bias=True),
 }
 
 
@@ -217,13 +220,44 @@ def _check_table_record(node: str, rec: "CPDRecord") -> None:
                          f"{int(counts.shape[1])} parent configurations")
 
 
+def _check_rff_record(node: str, rec: "CPDRecord") -> None:
+    """An ``rff_gaussian`` record the walk can run (csrc/vbn_walk_rff.h): fitted, with the random
+    features, the ridge solution and the standardisation buffers in the shapes the reference
+    registers them (rff_gaussian.py:42-63)."""
+    st = rec.state
+    n_in, d = int(rec.input_dim), int(rec.output_dim)
+    keys = ("mean_x", "std_x", "mean_y", "std_y", "_stats_ready", "_rff_w", "_rff_b", "_coef", "_bias", "_var")
+    for key in keys:
+        if key not in st:
+            raise ValueError(f"rff_gaussian node '{node}' {_OFF_PATH}: its checkpoint has no {key}")
+    if not bool(st["_stats_ready"]):
+        raise ValueError(f"rff_gaussian node '{node}' {_OFF_PATH}: it is not fitted (_stats_ready is False)")
+    f = int(st["_rff_w"].shape[0]) if st["_rff_w"].dim() == 2 else -1
+    want = {"mean_x": (n_in,), "std_x": (n_in,), "mean_y": (d,), "std_y": (d,), "_rff_w": (f, n_in),
+            "_rff_b": (f,), "_coef": (f, d), "_bias": (d,), "_var": (d,)}
+    if f < 1 or d < 1:
+        raise ValueError(f"rff_gaussian node '{node}' {_OFF_PATH}: _rff_w {tuple(st['_rff_w'].shape)} holds no "
+                         f"feature rows for {n_in} inputs and {d} output dims")
+    for key, shape in want.items():
+        if tuple(st[key].shape) != shape:
+            raise ValueError(f"rff_gaussian node '{node}' {_OFF_PATH}: {key} has shape {tuple(st[key].shape)}, "
+                             f"{shape} fits its {f} features, {n_in} inputs and {d} output dims")
+    nf = rec.hparams.get("n_features")
+    if nf is not None and int(nf) != f:
+        raise ValueError(f"rff_gaussian node '{node}' {_OFF_PATH}: n_features {nf} but _rff_w has {f} rows")
+
+
 def _check_table_model(topo: Sequence[str], parents: Mapping[str, Sequence[str]],
                        cpds: Mapping[str, "CPDRecord"]) -> None:
     """Refuse what the table walk cannot run: a ``categorical_table`` next to any other kind
-    (mixed networks are out of scope), an unfitted or inconsistent record, and a child whose
+    (mixed networks are out of scope), an unfitted or inconsistent record (``rff_gaussian`` records
+    are checked here too), and a child whose
     support of a parent column is not that column's set of valid class values -- with equal
     sets a sampled parent can never miss the child's support."""
     kinds = {cpds[n].kind for n in topo}
+    for n in topo:
+        if cpds[n].kind == "rff_gaussian":
+            _check_rff_record(n, cpds[n])
     if "categorical_table" not in kinds:
         return
     if len(kinds) > 1:
@@ -488,6 +522,37 @@ def random_init_model(g: nx.DiGraph, kinds: Mapping[str, str], data: Mapping[str
                 state["_weight"] = theta[:-1].contiguous()
                 state["_bias"] = theta[-1].contiguous()
                 state["_var"] = (x - xa @ theta).var(dim=0).clamp_min(1e-6)
+        elif kind == "rff_gaussian":
+            # the reference's constructor and closed-form fit (rff_gaussian.py:48-63, 148-181,
+            # 213-241) on ``data``: random features, then the ridge solution on [features, 1].  The
+            # normal equations are solved in float64 and rounded once: at ridge 1e-6 the Gram
+            # matrix of a one-parent node is beyond what a float32 solve resolves
+            f = int(hp["n_features"])
+            state["mean_x"] = par.mean(0) if par is not None else torch.zeros(0)
+            state["std_x"] = _std(par) if par is not None else torch.ones(0)
+            state["mean_y"] = x.mean(0)
+            state["std_y"] = _std(x)
+            state["_stats_ready"] = torch.tensor(True)
+            if d_in == 0:
+                state["_rff_w"] = torch.empty(f, 0)
+                state["_rff_b"] = torch.zeros(f)
+                state["_coef"] = torch.zeros(f, d_out)
+                state["_bias"] = torch.zeros(d_out)
+                state["_var"] = (state["std_y"] ** 2).clamp_min(1e-6)
+            else:
+                w = torch.randn(f, d_in, generator=gen) / max(float(hp["lengthscale"]), 1e-6)
+                b = 2 * math.pi * torch.rand(f, generator=gen)
+                feats = math.sqrt(2.0 / f) * torch.cos(((par - state["mean_x"]) / state["std_x"]) @ w.t() + b)
+                y = (x - state["mean_y"]) / state["std_y"]
+                fa = (torch.cat([feats, torch.ones(feats.shape[0], 1)], dim=1) if hp["use_bias"] else feats).double()
+                reg = float(hp["ridge"]) * torch.eye(fa.shape[1], dtype=torch.float64)
+                theta = (torch.linalg.solve(fa.t() @ fa + reg, fa.t() @ y.double()) if float(hp["ridge"]) > 0
+                         else torch.linalg.lstsq(fa, y.double()).solution).float()
+                coef, bias = (theta[:-1], theta[-1]) if hp["use_bias"] else (theta, torch.zeros(d_out))
+                state["_rff_w"], state["_rff_b"] = w, b
+                state["_coef"], state["_bias"] = coef.contiguous(), bias.contiguous()
+                state["_var"] = (y - (feats @ coef + bias)).var(dim=0, unbiased=False).clamp_min(1e-6) \
+                    * state["std_y"] ** 2
         elif kind == "mdn":
             k = int(hp["n_components"])
             if d_in == 0:

@@ -29,13 +29,15 @@ import torch.nn.functional as F
 from .model import BNModel, CPDRecord
 
 # ---- the values of include/vbn_hip_types.h and csrc/*.h (tests/test_layout_constants.py compares) ----
-KIND_ID = {"gaussian_nn": 0, "linear_gaussian": 1, "mdn": 2, "kde": 3, "softmax_nn": 4, "categorical_table": 5}
-# kind-set bits (VBN_KM_*): bits 0-4 = 1 << kind of every CPD kind walked, then
+KIND_ID = {"gaussian_nn": 0, "linear_gaussian": 1, "mdn": 2, "kde": 3, "softmax_nn": 4, "categorical_table": 5,
+           "rff_gaussian": 6}
+# kind-set bits (VBN_KM_*): bits 0-4 = 1 << kind of every CPD kind walked (kinds 0-4), then
 KM_NONRELU = 32           # some NN CPD has a non-relu activation
 KM_HALFWAVE = 64          # half-wave launch (wave_particles 32)
 KM_LEAN = 128             # no injected draws, no segment state, not Gibbs
 KM_NOISELESS = 256        # no injected draws (production Gibbs sweeps)
-KM_GENERIC_MLP = 512      # some NN CPD has hidden_dims other than (32, 32)
+KM_GENERIC_MLP = 512      # some step runs out of line: an NN CPD with hidden_dims other than (32, 32),
+                          # or an rff_gaussian node
 KM_TABLE = 1024           # kind_mask of a plan whose walked steps are all categorical_table
 KM_KINDS = 63             # the plan's CPD kinds and KM_NONRELU
 KM_NN_KINDS = 21          # any NN kind: gaussian_nn | mdn | softmax_nn
@@ -438,23 +440,32 @@ def _np(t: torch.Tensor) -> np.ndarray:
     return t.detach().to("cpu", torch.float32).numpy()
 
 
+def _mfma_fragments(w: np.ndarray, b: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """A layer ``w [out, in]``, ``b [out]`` as v_mfma_f32_32x32x2_f32 operands, zero-padded: the A
+    fragments [ceil(out/32)][ceil(in/2)][64] (lane l: w[32 blk + (l & 31)][2 t + (l >> 5)]) and the
+    bias as the accumulator's initial value [ceil(out/32)][2][16] (b[32 blk + row(r, h)])."""
+    lane = np.arange(64)
+    out, nin = w.shape
+    nblk, t1 = -(-out // 32), -(-nin // 2)
+    wz = np.zeros((nblk * 32, 2 * t1), np.float32)
+    wz[:out, :nin] = w
+    frag = np.stack([np.stack([wz[32 * k + (lane & 31), 2 * t + (lane >> 5)] for t in range(t1)])
+                     for k in range(nblk)])                                       # [nblk, t1, 64]
+    bz = np.zeros(nblk * 32, np.float32)
+    bz[:out] = b
+    bias = np.stack([bz[32 * k + _ROWS] for k in range(nblk)])                    # [nblk, 2, 16]
+    return frag, bias
+
+
 def _pack_mlp_generic(blob: _Blob, layers, offs: Dict[str, int]) -> Dict[str, int]:
     """Layer table + fragments of csrc mlp_generic (hidden_dims other than (32, 32)): per
     layer W fragments [ceil(out/32)][ceil(in/2)][64] and accumulator-init biases
     [ceil(out/32)][2][16]; the table [L, (in, out, off_w, off_b) x L] is int32 in the blob."""
-    lane = np.arange(64)
     table = [len(layers)]
     for w, b in layers:
         w, b = _np(w), _np(b)
         out, nin = w.shape
-        nblk, t1 = -(-out // 32), -(-nin // 2)
-        wz = np.zeros((nblk * 32, 2 * t1), np.float32)
-        wz[:out, :nin] = w
-        frag = np.stack([np.stack([wz[32 * k + (lane & 31), 2 * t + (lane >> 5)] for t in range(t1)])
-                         for k in range(nblk)])                                   # [nblk, t1, 64]
-        bz = np.zeros(nblk * 32, np.float32)
-        bz[:out] = b
-        bias = np.stack([bz[32 * k + _ROWS] for k in range(nblk)])                # [nblk, 2, 16]
+        frag, bias = _mfma_fragments(w, b)
         table += [nin, out, blob.add(frag), blob.add(bias)]
     offs["w2"] = blob.add(np.asarray(table, np.int32).view(np.float32))
     offs["n_out"] = int(_np(layers[-1][0]).shape[0])
@@ -548,6 +559,39 @@ def _pack_mlp(blob: _Blob, rec: CPDRecord, standardize: bool) -> Dict[str, int]:
     return offs
 
 
+def rff_coef_rows(coef: np.ndarray) -> np.ndarray:
+    """``coef [F, D]`` of an rff_gaussian node by feature row in the MFMA accumulator's row order:
+    [ceil(F/32)][half 2][D][16] = coef[32 blk + row(r, h)][d], zero-padded, so that a lane reads the
+    16 feature rows it holds after the MFMA contiguously per output dim (csrc/vbn_walk_rff.h)."""
+    f, d = coef.shape
+    nblk = -(-f // 32)
+    cz = np.zeros((nblk * 32, d), np.float32)
+    cz[:f] = coef
+    return np.stack([np.stack([cz[32 * k + _ROWS[h]].T for h in range(2)]) for k in range(nblk)])
+
+
+def _pack_rff(blob: _Blob, rec: CPDRecord) -> Dict[str, int]:
+    """Blocks of an rff_gaussian node (csrc/vbn_walk_rff.h step_rff_gaussian): the standardisation
+    block of gaussian_nn, ``_rff_w`` / ``_rff_b`` as the MFMA fragments of :func:`_mfma_fragments`,
+    ``_coef`` in accumulator row order, and the tail bias, std_y, mean_y, scale, log_scale with
+    scale = sqrt(clamp(_var, min_scale^2)) in the reference's float32 ops (rff_gaussian.py:183-185).
+    A root packs the tail only."""
+    st = rec.state
+    scale = torch.sqrt(st["_var"].float().clamp(min=float(rec.hp("min_scale")) ** 2))
+    offs: Dict[str, int] = {}
+    offs["tail"] = blob.add(np.concatenate([_np(st["_bias"]), _np(st["std_y"]), _np(st["mean_y"]), _np(scale),
+                                            _np(torch.log(scale))]))
+    if rec.is_root:
+        return offs
+    inv = (np.float32(1.0) / _np(st["std_x"]).astype(np.float32)).astype(np.float32)
+    offs["std"] = blob.add(np.concatenate([_np(st["mean_x"]), inv]))
+    frag, bias = _mfma_fragments(_np(st["_rff_w"]), _np(st["_rff_b"]))
+    offs["w1"] = blob.add(frag)
+    offs["b2"] = blob.add(bias)
+    offs["w3"] = blob.add(rff_coef_rows(_np(st["_coef"])))
+    return offs
+
+
 def _pack_table(blob: _Blob, rec: CPDRecord) -> Dict[str, int]:
     """Rows of a categorical_table node for csrc/vbn_table_walk.hip, computed with the reference's
     own float32 torch ops for every parent configuration at once (categorical_table.py:359-377:
@@ -630,6 +674,12 @@ def _pack_node(blob: _Blob, rec: CPDRecord) -> NodePack:
         k, aux0, aux1 = offs.pop("_table")
         return NodePack(kind=KIND_ID[kind], flags=flags, act=0, n_in=rec.input_dim, out_dim=D, k=k, n_out=0,
                         aux0=aux0, aux1=aux1, offs=offs, scratch=0)
+    if kind == "rff_gaussian":
+        # k = the feature count; no weight block (the fragments are read from the blob); the
+        # features stay in registers, the D scratch rows hold loc
+        return NodePack(kind=KIND_ID[kind], flags=flags | (0 if root else F_STANDARDIZE), act=0, n_in=rec.input_dim,
+                        out_dim=D, k=int(st["_rff_w"].shape[0]), n_out=0, aux0=0, aux1=0,
+                        offs=_pack_rff(blob, rec), scratch=0 if root else D)
     act = ACT_ID.get(str(rec.hp("activation") or "relu"), -1)
     if act < 0:
         raise ValueError(f"unknown activation {rec.hp('activation')}")
@@ -888,7 +938,7 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
     the MLPs' hidden layer on the exact f32 MFMA chain instead of the split-f16 product;
     ``kde_valu``: KDE pairwise distances on packed VALU instead of the 16x16x4 f32 MFMA tile.
     ``params``: nodes whose conditional parameters are written instead of a draw (role
-    PARAMS; gaussian_nn / linear_gaussian: loc ++ scale, softmax_nn: class probabilities
+    PARAMS; gaussian_nn / linear_gaussian / rff_gaussian: loc ++ scale, softmax_nn: class probabilities
     [D][C], mdn: softmax(logits) [K] ++ loc [K][D] ++ scale [K][D]) -- the Rao-Blackwellized
     target and CPDHandle.conditional.  ``pre_out``: latent nodes that write their per-sample
     quantities instead of a sample (VBN_F_PRE_OUT, the shared-sample pre-pass of
@@ -929,7 +979,7 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
         if n not in params_s:
             return model.out_dim(n)
         rec = model.cpds[n]
-        if rec.kind in ("gaussian_nn", "linear_gaussian"):
+        if rec.kind in ("gaussian_nn", "linear_gaussian", "rff_gaussian"):
             return 2 * model.out_dim(n)                               # loc ++ scale
         if rec.kind == "softmax_nn":
             return model.out_dim(n) * int(rec.hp("n_classes"))        # class probabilities [D][C]
@@ -1060,6 +1110,9 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
     for n in order:
         if n in latent_s or n in logp_s or n in params_s:
             npk = packed.nodes[n]
+            if npk.kind == KIND_ID["rff_gaussian"]:       # out of line like a generic MLP: kind-set
+                kind_mask |= KM_GENERIC_MLP               # bit 9, no kind bit of its own
+                continue
             kind_mask |= 1 << npk.kind
             if npk.n_out and npk.act != ACT_ID["relu"]:
                 kind_mask |= KM_NONRELU
@@ -1288,7 +1341,8 @@ _GIBBS_COST_MLP, _GIBBS_COST_ROOT, _GIBBS_COST_SELECT, _GIBBS_COST_BARRIER = 1.0
 def _gibbs_step_cost(r) -> float:
     if int(r[S_ROLE]) == ROLE_SELECT:
         return _GIBBS_COST_SELECT
-    heavy = int(r[S_WBLK_LEN]) > 0 or int(r[S_KIND]) == KIND_ID["kde"]
+    heavy = int(r[S_WBLK_LEN]) > 0 or int(r[S_KIND]) == KIND_ID["kde"] or (
+        int(r[S_KIND]) == KIND_ID["rff_gaussian"] and int(r[S_NIN]) > 0)
     return _GIBBS_COST_MLP if heavy else _GIBBS_COST_ROOT
 
 
