@@ -23,8 +23,10 @@ enum vbn_kind {
   VBN_KIND_KDE = 3,
   VBN_KIND_SOFTMAX_NN = 4,
   VBN_KIND_CATEGORICAL_TABLE = 5, /* walked by vbn_hip_table_walk only (csrc/vbn_table_walk.hip) */
-  VBN_KIND_RFF_GAUSSIAN = 6       /* random Fourier feature regressor (csrc/vbn_walk_rff.h); its plans
+  VBN_KIND_RFF_GAUSSIAN = 6,      /* random Fourier feature regressor (csrc/vbn_walk_rff.h); its plans
                                      set VBN_KM_GENERIC_MLP, not a kind bit of their own */
+  VBN_KIND_CATEGORICAL_EMBEDDED_SOFTMAX = 7 /* walked by vbn_hip_table_walk only, next to
+                                     categorical_table steps (csrc/vbn_table_embed.h) */
 };
 
 /* role of a node for one query signature */
@@ -106,6 +108,8 @@ enum vbn_mode {
 #define VBN_KM_GENERIC_MLP 512   /* some step runs out of line: an NN CPD with hidden_dims other
                                     than (32, 32) (mlp_generic) or an rff_gaussian node           */
 #define VBN_KM_TABLE 1024        /* alone: every step is a categorical_table (vbn_hip_table_walk) */
+#define VBN_KM_EMBED 2048        /* with VBN_KM_TABLE: some step is a categorical_embedded_softmax
+                                    (vbn_hip_table_walk's embedded instantiation)              */
 #define VBN_KM_KINDS 63          /* the plan's CPD kinds and VBN_KM_NONRELU                    */
 #define VBN_KM_NN_KINDS 21       /* any NN kind: gaussian_nn | mdn | softmax_nn                */
 #define VBN_KM_UNSTAGED_KINDS 28 /* mdn | kde | softmax_nn: sets that read weights from the blob */
@@ -171,8 +175,9 @@ typedef struct vbn_walk_args {
   int32_t n_out_cols;
   int32_t mode;            /* enum vbn_mode                                        */
   int32_t kind_mask;       /* CPD kinds walked: 1<<kind (kinds 0-4), | VBN_KM_NONRELU, | VBN_KM_GENERIC_MLP;
-                              VBN_KM_TABLE alone: every step is a categorical_table
-                              (vbn_hip_table_walk; vbn_hip_walk refuses it)             */
+                              VBN_KM_TABLE alone: every step is a categorical_table,
+                              VBN_KM_TABLE | VBN_KM_EMBED: some are categorical_embedded_softmax
+                              (vbn_hip_table_walk; vbn_hip_walk refuses both)           */
   int64_t q_base;          /* global index of query 0 (multi-GPU shards)            */
   uint64_t seed;
   uint64_t offset;         /* RNG stream offset (one per engine call)               */

@@ -26,7 +26,7 @@ import torch
 
 from .engines import Query, infer_batch_size
 from .handle import CPDHandle
-from .model import BNModel, checkpoint_from_model, load_checkpoint, model_from_checkpoint, model_from_vbn
+from .model import DISCRETE_KINDS, BNModel, checkpoint_from_model, load_checkpoint, model_from_checkpoint, model_from_vbn
 from .registry import INFERENCE_REGISTRY, SAMPLING_REGISTRY
 
 __all__ = ["VBN", "ConfigItem", "defaults"]
@@ -320,8 +320,9 @@ class VBN:
                   "likelihood_weighting": "is_lw", "ancestral": "ancestral"}
         if method not in ops_of:
             raise ValueError(f"pack_query: method must be one of {sorted(ops_of)}")
-        if any(rec.kind == "categorical_table" for rec in self.model.cpds.values()):
-            raise NotImplementedError("pack_query is not implemented for categorical_table networks: their walk "
+        kinds = [k for k in DISCRETE_KINDS if any(rec.kind == k for rec in self.model.cpds.values())]
+        if kinds:
+            raise NotImplementedError(f"pack_query is not implemented for {' / '.join(kinds)} networks: their walk "
                                       "has no packed-plan form yet (use infer_posterior / sample)")
         names = {k: list(signature.get(k) or []) for k in ("evidence", "do")}
         q = self._normalize_query({"target": signature.get("target"),

@@ -30,15 +30,22 @@
 // Tables small enough (tw_shape below) are staged once per workgroup into LDS with
 // global_load_lds_dwordx4 and gathered from there; larger blobs are gathered from global / L2.
 // Both paths read the same floats and run the same arithmetic: identical outputs.
+//
+// Plans with categorical_embedded_softmax steps (kind_mask VBN_KM_TABLE | VBN_KM_EMBED) run the
+// EMBED instantiation: the same walk plus the step of vbn_table_embed.h, which evaluates the
+// node's MLP per particle on MFMA and needs max_out rows of LDS scratch per wave for the logits.
+// It reads tables and weights from global / L2 only.  All-table plans keep the two instantiations
+// above, whose code the EMBED parameter does not touch.
 #include "vbn_hip.h"
 #include "vbn_walk_common.h"
+#include "vbn_table_embed.h"
 
 #include <stdlib.h>
 
 #define TW_WAVES 4
 #define TW_ROW_VEC 8       // rows of at most this many floats: every entry compared (float4 loads)
 
-template <bool STAGED>
+template <bool STAGED, bool EMBED>
 __global__ void __launch_bounds__(TW_WAVES* WAVE)
 vbn_table_walk_kernel(const vbn_walk_args A, const float* __restrict__ params, const vbn_step* __restrict__ steps,
                       const int32_t* __restrict__ in_cols, const int blob_floats) {
@@ -85,6 +92,15 @@ vbn_table_walk_kernel(const vbn_walk_args A, const float* __restrict__ params, c
   float lp = 0.f;
   for (int i = 0; i < A.n_steps; ++i) {
     const vbn_step st = steps[i];                    // wave-uniform: scalar loads
+    if constexpr (EMBED) {
+      if (st.kind == VBN_KIND_CATEGORICAL_EMBEDDED_SOFTMAX) {
+        if (st.role == VBN_ROLE_SKIP) continue;
+        // logit scratch rows of this wave, after every wave's class-index slots
+        float* scr = smem + ((size_t)nw * A.n_slots + (size_t)wave * A.max_out) * WAVE;
+        lp += embed_step(A, st, params, in_cols, idx, scr, L, blob_floats);
+        continue;
+      }
+    }
     if (st.kind != VBN_KIND_CATEGORICAL_TABLE || st.role == VBN_ROLE_SKIP) continue;
     const int C = max(st.k, 1), P = max(st.aux0, 1), Cp = max(st.aux1, C), D = st.out_dim;
     const bool reads = st.role != VBN_ROLE_FIXED || (st.flags & VBN_F_LOGP);
@@ -193,9 +209,11 @@ static int tw_check(const vbn_walk_args* a) {
   if (!a || (!a->steps && a->n_steps > 0) || a->n_steps < 0 || !a->params || a->n_samples <= 0 ||
       a->n_queries <= 0 || a->n_slots <= 0 || !a->in_cols)
     return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: bad arguments");
-  if (a->kind_mask != VBN_KM_TABLE)
+  if (a->kind_mask != VBN_KM_TABLE && a->kind_mask != (VBN_KM_TABLE | VBN_KM_EMBED))
     return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: only plans whose every step is a categorical_table "
-                                "(kind_mask 1024)");
+                                "(kind_mask 1024) or a categorical_embedded_softmax (kind_mask 3072)");
+  if ((a->kind_mask & VBN_KM_EMBED) && a->max_out <= 0)
+    return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: an embedded plan needs max_out logit scratch rows");
   if (a->state || a->state_flags || a->precomp_q || a->stats_part || a->wave_particles == 32 ||
       (a->mode != VBN_MODE_MCM && a->mode != VBN_MODE_WEIGHTED && a->mode != VBN_MODE_SAMPLE))
     return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: segment state, precomputed quantities, fused statistics, "
@@ -211,7 +229,9 @@ static int tw_check(const vbn_walk_args* a) {
 }
 
 static int tw_shape(const vbn_walk_args* a, tw_launch* out) {
-  const int64_t per_wave = (int64_t)a->n_slots * WAVE * (int64_t)sizeof(int32_t);
+  const bool embed = (a->kind_mask & VBN_KM_EMBED) != 0;
+  // an embedded plan adds max_out rows of logit scratch per wave and never stages
+  const int64_t per_wave = ((int64_t)a->n_slots + (embed ? a->max_out : 0)) * WAVE * (int64_t)sizeof(int32_t);
   const int64_t tab_bytes = (int64_t)a->wbuf_floats * (int64_t)sizeof(float);
   int nw = TW_WAVES;
   while (nw > 1 && nw * per_wave > TW_LDS_WG_MAX) nw >>= 1;
@@ -224,7 +244,7 @@ static int tw_shape(const vbn_walk_args* a, tw_launch* out) {
   const char* env_s = getenv("VBN_TABLE_STAGE");
   const bool force_stage = env_s && env_s[0] && env_s[0] != '0';
   out->nw = nw;
-  out->stage = !force_global && nw == TW_WAVES && staged <= TW_LDS_WG_MAX &&
+  out->stage = !embed && !force_global && nw == TW_WAVES && staged <= TW_LDS_WG_MAX &&
                (force_stage || std::min<int64_t>(TW_WG_PER_CU, TW_LDS_CU / staged) ==
                                    std::min<int64_t>(TW_WG_PER_CU, TW_LDS_CU / plain));
   out->lds = (size_t)(out->stage ? staged : plain);
@@ -241,11 +261,14 @@ extern "C" int vbn_hip_table_walk(const vbn_walk_args* a, void* stream) {
   const int64_t blocks = (total + (int64_t)WAVE * w.nw - 1) / ((int64_t)WAVE * w.nw);
   if (blocks > 0x7fffffffLL) return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: too many particles for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (w.stage)
-    hipLaunchKernelGGL(vbn_table_walk_kernel<true>, dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
+  if (a->kind_mask & VBN_KM_EMBED)
+    hipLaunchKernelGGL((vbn_table_walk_kernel<false, true>), dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
+                       a->params, a->steps, a->in_cols, a->wbuf_floats);
+  else if (w.stage)
+    hipLaunchKernelGGL((vbn_table_walk_kernel<true, false>), dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
                        a->params, a->steps, a->in_cols, a->wbuf_floats);
   else
-    hipLaunchKernelGGL(vbn_table_walk_kernel<false>, dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
+    hipLaunchKernelGGL((vbn_table_walk_kernel<false, false>), dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
                        a->params, a->steps, a->in_cols, a->wbuf_floats);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return vbn_fail((int)e, hipGetErrorString(e));

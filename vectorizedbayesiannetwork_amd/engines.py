@@ -43,8 +43,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from .model import BNModel, model_from_vbn
-from .plan import (F_PRE_OUT, KIND_ID, KM_GENERIC_MLP, KM_UNSTAGED_KINDS, MODE_MCM, MODE_SAMPLE, MODE_WEIGHTED,
+from .model import DISCRETE_KINDS, BNModel, model_from_vbn
+from .plan import (F_PRE_OUT, KIND_ID, KM_EMBED, KM_GENERIC_MLP, KM_UNSTAGED_KINDS, MODE_MCM, MODE_SAMPLE, MODE_WEIGHTED,
                    S_FLAGS, S_KIND, GibbsPlan, PackedModel, QueryPlan, barren_pruned,
                    liveness_order, precompute_plans,
                    build_gibbs_plan, build_plan)
@@ -241,8 +241,10 @@ def _check_discrete(pk: PackedModel, vals: Dict[str, torch.Tensor], nodes: Seque
 def _no_tables(vbn, what: str) -> None:
     """Engines the table walk does not serve yet (follow-ups: they need segment state, the RB
     epilogue or Gibbs sweeps in csrc/vbn_table_walk.hip); raised before anything touches the GPU."""
-    if any(rec.kind == "categorical_table" for rec in model_from_vbn(vbn).cpds.values()):
-        raise NotImplementedError(f"{what} is not implemented for categorical_table networks")
+    kinds = {rec.kind for rec in model_from_vbn(vbn).cpds.values()}
+    mine = [k for k in DISCRETE_KINDS if k in kinds]
+    if mine:
+        raise NotImplementedError(f"{what} is not implemented for {' / '.join(mine)} networks")
 
 
 def _check_table_support(pk: PackedModel, plan: QueryPlan, fixed: torch.Tensor) -> None:
@@ -523,7 +525,7 @@ def _run_table_walk(pk, plan, fixed, b, n, *, seed, offset, q_base, noise, noise
                            q_base=q_base)
     args = (plan.steps, plan.in_cols, pk.params, fixed, noise, plan.table_out_cols, b, n, plan.n_slots,
             plan.fixed_ld, fixed_per_particle, noise_b, len(plan.noise_nodes), pk.dmax, n_out_cols, plan.mode,
-            q_base, seed, offset, want_lp)
+            q_base, seed, offset, want_lp, plan.max_out if plan.kind_mask & KM_EMBED else 0)
     if run_if is None and out_x is None:
         lp, x = ops.table_walk(*args)
     else:
@@ -901,16 +903,21 @@ class CategoricalExact:
                     vals[target].unsqueeze(1).expand(b, 1, -1))
         parents = model.parents[target]
         rec = model.cpds[target]
-        if (not all(p in vals for p in parents) or rec.kind != "categorical_table"   # 106-125
+        if (not all(p in vals for p in parents) or rec.kind not in DISCRETE_KINDS    # 106-125
                 or model.out_dim(target) != 1):
             return self._fallback_infer(vbn, query, **kwargs)
+        support = rec.state["_sample_values"][0].to(device=dev, dtype=torch.float32)   # 81-82
+        if rec.kind == "categorical_embedded_softmax" and not parents:
+            # 58-66: a root's probabilities are softmax(_logits) as stored -- the reference does not
+            # fill the masked classes here, unlike sample / log_prob (one row, no walk needed)
+            probs = torch.softmax(rec.state["_logits"].to(device=dev, dtype=torch.float32), dim=-1)
+            return probs.expand(b, -1), support.view(1, -1, 1).expand(b, -1, 1)
         nodes = set(parents) | {target}
         plan = _plan(pk, ("cat-exact", target), latent=[], fixed=[x for x in model.topo if x in parents], logp=[],
                      out_nodes=[target], params=[target], shared_roots=True, mode=MODE_SAMPLE,
                      skip=[x for x in model.topo if x not in nodes])
         fx = _fixed_buffer(plan, vals, b, dev)
         _, probs = run_walk(pk, plan, fx, b, 1, seed=0, q_base=self.q_base)
-        support = rec.state["_sample_values"][0].to(device=dev, dtype=torch.float32)   # 81-82
         return probs.view(b, -1), support.view(1, -1, 1).expand(b, -1, 1)
 
 

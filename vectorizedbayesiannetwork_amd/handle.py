@@ -9,7 +9,7 @@ the reference's formats (``cpd_handle.py:348-404``):
   (walk role PARAMS);
 * ``mixture_params``  -- mdn: ``weights`` = softmax(logits) [B, 1, K], ``loc`` / ``scale``
   [B, 1, K, D] (PARAMS);
-* ``categorical_probs`` -- softmax_nn, categorical_table: ``probs`` [B, 1, D, C], ``k``,
+* ``categorical_probs`` -- softmax_nn, categorical_table, categorical_embedded_softmax: ``probs`` [B, 1, D, C], ``k``,
   ``support`` (``_sample_values``) (PARAMS);
 * ``empirical_samples`` -- kde: ``n_samples`` GPU draws with their mean / std.
 
@@ -30,7 +30,7 @@ __all__ = ["CPDHandle", "to_serializable"]
 
 _CLASS_NAME = {"gaussian_nn": "GaussianNNCPD", "linear_gaussian": "LinearGaussianCPD", "mdn": "MDNCPD",
                "kde": "KDECPD", "softmax_nn": "SoftmaxNNCPD", "categorical_table": "CategoricalTableCPD",
-               "rff_gaussian": "RFFGaussianCPD"}
+               "rff_gaussian": "RFFGaussianCPD", "categorical_embedded_softmax": "CategoricalEmbeddedSoftmaxCPD"}
 # kinds whose conditional is one normal per output dim (PARAMS: loc ++ scale)
 _NORMAL_KINDS = ("gaussian_nn", "linear_gaussian", "rff_gaussian")
 
@@ -214,8 +214,8 @@ class CPDHandle:
             return {"format": "mixture_params", "weights": prm[..., :k],
                     "loc": prm[..., k:k + k * D].reshape(b, s, k, D),
                     "scale": prm[..., k + k * D:].reshape(b, s, k, D)}
-        if kind == "categorical_table":          # n_classes = 0 means "as fitted": the table's width
-            c = int(self._rec.state["_counts"].shape[-1])
+        if kind in ("categorical_table", "categorical_embedded_softmax"):   # n_classes = 0 means "as fitted"
+            c = int(self._rec.state["_class_values"].shape[-1])
         else:
             c = int(self._rec.hp("n_classes"))
         return {"format": "categorical_probs", "probs": prm.reshape(b, s, D, c), "k": c,

@@ -11,10 +11,13 @@ The accelerated path never imports the reference. It consumes either
   (reference ``core/base.py:66-81``); or
 * :func:`random_init_model`, which builds random-init weights of the reference
   architectures (the bench's synthetic models); or
-* :func:`random_table_model`, seeded random count tables of ``categorical_table`` CPDs.
+* :func:`random_table_model`, seeded random count tables of ``categorical_table`` CPDs; or
+* :func:`random_embed_model`, seeded random ``categorical_embedded_softmax`` CPDs (optionally
+  next to tables).
 
-``categorical_table`` networks run on a walk of their own (``csrc/vbn_table_walk.hip``), so a
-model is either all ``categorical_table`` or holds none: mixed networks are refused at load.
+Discrete networks (``categorical_table`` and ``categorical_embedded_softmax`` CPDs, in any
+mixture) run on a walk of their own (``csrc/vbn_table_walk.hip``), so a model is either all
+discrete or holds no discrete CPD: mixed networks are refused at load.
 """
 from __future__ import annotations
 
@@ -35,12 +38,19 @@ __all__ = [
     "record_from_cpd",
     "random_init_model",
     "random_table_model",
+    "random_embed_model",
     "checkpoint_from_model",
     "KIND_DEFAULTS",
 ]
 
 # Registry keys of the reference CPDs on the hot path (reference core/registry.py + cpds/*).
-CPD_KINDS = ("gaussian_nn", "linear_gaussian", "mdn", "kde", "softmax_nn", "categorical_table", "rff_gaussian")
+CPD_KINDS = ("gaussian_nn", "linear_gaussian", "mdn", "kde", "softmax_nn", "categorical_table", "rff_gaussian",
+             "categorical_embedded_softmax")
+# the kinds of the discrete walk (csrc/vbn_table_walk.hip)
+DISCRETE_KINDS = ("categorical_table", "categorical_embedded_softmax")
+# widest hidden layer the embedded step keeps in registers (csrc/vbn_table_embed.h EMBED_NB * 32)
+EMBED_MAX_HIDDEN = 64
+EMBED_ACTIVATIONS = ("relu", "tanh", "gelu", "elu")
 
 _CLASS_TO_KIND = {
     "GaussianNNCPD": "gaussian_nn",
@@ -50,6 +60,7 @@ _CLASS_TO_KIND = {
     "SoftmaxNNCPD": "softmax_nn",
     "CategoricalTableCPD": "categorical_table",
     "RFFGaussianCPD": "rff_gaussian",
+    "CategoricalEmbeddedSoftmaxCPD": "categorical_embedded_softmax",
 }
 
 # Constructor defaults of the reference classes (gaussian_nn.py:41-50, linear_gaussian.py:14-22,
@@ -67,6 +78,10 @@ KIND_DEFAULTS: Dict[str, Dict[str, Any]] = {
     "categorical_table": dict(n_classes=0, parent_n_classes=None, alpha=1.0, alpha_mode="per_class",
                               prior="uniform"),
     "rff_gaussian": dict(n_features=256, lengthscale=1.0, ridge=1e-6, min_scale=1e-3, use_bias=True),
+    # categorical_embedded_softmax.py:51-65
+    "categorical_embedded_softmax": dict(n_classes=0, parent_n_classes=None, embedding_dim=8, hidden_dims=(64, 64),
+                                         activation="relu", label_smoothing=0.0, class_weighting="none",
+                                         max_grad_norm=None),
 }
 
 # The packaged YAML defaults the reference's ``defaults.cpd(kind)`` returns
@@ -80,6 +95,8 @@ YAML_DEFAULTS: Dict[str, Dict[str, Any]] = {
                        min_bin_width=1e-12, binning="quantile", within_bin="triangular"),
     "categorical_table": dict(n_classes=0, alpha=1.0, alpha_mode="total_mass", prior="global"),
     "rff_gaussian": dict(n_features=256, lengthscale=1.0, ridge=1e-6, min_scale=1e-3, use_bias=True),
+    "categorical_embedded_softmax": dict(n_classes=0, embedding_dim=8, hidden_dims=(64, 64), activation="relu",
+                                         label_smoothing=0.0, class_weighting="none"),
 }
 
 
@@ -220,6 +237,65 @@ def _check_table_record(node: str, rec: "CPDRecord") -> None:
                          f"{int(counts.shape[1])} parent configurations")
 
 
+def _check_embed_record(node: str, rec: "CPDRecord") -> None:
+    """A ``categorical_embedded_softmax`` record the embedded step can run (csrc/vbn_table_embed.h):
+    fitted, sorted valid class values in front of the masked ones, one embedding table per parent
+    column, an MLP whose shapes chain from ``n_in * embedding_dim`` to ``D * C`` with hidden layers
+    of at most EMBED_MAX_HIDDEN units and an activation the kernel implements; roots carry
+    ``_logits [D, C]`` instead of a network."""
+    who = f"categorical_embedded_softmax node '{node}' {_OFF_PATH}"
+    st = rec.state
+    for key in ("_class_values", "_class_mask", "_stats_ready"):
+        if key not in st:
+            raise ValueError(f"{who}: its checkpoint has no {key}")
+    if not bool(st["_stats_ready"]):
+        raise ValueError(f"{who}: it is not fitted (_stats_ready is False)")
+    cv, mask = st["_class_values"], st["_class_mask"].bool()
+    d, n_in = int(rec.output_dim), int(rec.input_dim)
+    if cv.dim() != 2 or cv.shape[0] != d or mask.shape != cv.shape or cv.shape[1] < 1:
+        raise ValueError(f"{who}: _class_values {tuple(cv.shape)} and _class_mask {tuple(mask.shape)} do not fit "
+                         f"{d} output dims")
+    c = int(cv.shape[1])
+    for k in range(d):
+        nv = int(mask[k].sum())
+        vals = cv[k][:nv]
+        if nv < 1 or not bool(mask[k][:nv].all()) or (nv > 1 and not bool((vals[1:] > vals[:-1]).all())):
+            raise ValueError(f"{who}: dim {k} needs its valid class values sorted in front of the masked ones")
+    if n_in == 0:
+        if "_logits" not in st or tuple(st["_logits"].shape) != (d, c):
+            raise ValueError(f"{who}: a root needs _logits of shape {(d, c)}")
+        return
+    act = str(rec.hp("activation"))
+    if act not in EMBED_ACTIVATIONS:
+        raise ValueError(f"{who}: activation '{act}' is not implemented (one of {list(EMBED_ACTIVATIONS)})")
+    extra = rec.extra or {}
+    pv, cards = extra.get("parent_values"), extra.get("parent_cards")
+    if pv is None or cards is None or not (len(pv) == len(cards) == n_in):
+        raise ValueError(f"{who}: no parent support for its {n_in} parent columns")
+    if any(int(k) != int(v.numel()) or int(k) < 1 for k, v in zip(cards, pv)):
+        raise ValueError(f"{who}: parent_cards do not match parent_values")
+    e = int(rec.hp("embedding_dim"))
+    for j in range(n_in):
+        w = st.get(f"embeddings.{j}.weight")
+        if w is None or tuple(w.shape) != (int(cards[j]), e):
+            raise ValueError(f"{who}: embeddings.{j}.weight "
+                             f"{None if w is None else tuple(w.shape)} is not [{int(cards[j])}, {e}]")
+    layers = rec.mlp_layers()
+    if not layers:
+        raise ValueError(f"{who}: its checkpoint has no net")
+    width = n_in * e
+    for i, (w, b) in enumerate(layers):
+        if w.dim() != 2 or int(w.shape[1]) != width or tuple(b.shape) != (int(w.shape[0]),):
+            raise ValueError(f"{who}: layer {i} has weight {tuple(w.shape)} and bias {tuple(b.shape)} after a "
+                             f"width of {width}")
+        width = int(w.shape[0])
+        if i + 1 < len(layers) and width > EMBED_MAX_HIDDEN:
+            raise ValueError(f"{who}: a hidden layer of {width} units (the kernel keeps at most "
+                             f"{EMBED_MAX_HIDDEN} in registers)")
+    if width != d * c:
+        raise ValueError(f"{who}: the network ends in {width} logits, {d} dims x {c} classes need {d * c}")
+
+
 def _check_rff_record(node: str, rec: "CPDRecord") -> None:
     """An ``rff_gaussian`` record the walk can run (csrc/vbn_walk_rff.h): fitted, with the random
     features, the ridge solution and the standardisation buffers in the shapes the reference
@@ -258,14 +334,19 @@ def _check_table_model(topo: Sequence[str], parents: Mapping[str, Sequence[str]]
     for n in topo:
         if cpds[n].kind == "rff_gaussian":
             _check_rff_record(n, cpds[n])
-    if "categorical_table" not in kinds:
+    if not kinds & set(DISCRETE_KINDS):
         return
-    if len(kinds) > 1:
-        other = sorted(kinds - {"categorical_table"})
-        raise ValueError(f"a model that mixes categorical_table with {other} {_OFF_PATH}: the table walk runs "
-                         "networks whose every CPD is a categorical_table (mixed networks are out of scope)")
+    if kinds - set(DISCRETE_KINDS):
+        other = sorted(kinds - set(DISCRETE_KINDS))
+        mine = " / ".join(k for k in DISCRETE_KINDS if k in kinds)
+        raise ValueError(f"a model that mixes {mine} with {other} {_OFF_PATH}: the table walk runs "
+                         "networks whose every CPD is a categorical_table or a categorical_embedded_softmax "
+                         "(mixed networks are out of scope)")
     for n in topo:
-        _check_table_record(n, cpds[n])
+        if cpds[n].kind == "categorical_table":
+            _check_table_record(n, cpds[n])
+        else:
+            _check_embed_record(n, cpds[n])
     for n in topo:
         rec = cpds[n]
         pv = (rec.extra or {}).get("parent_values") or []
@@ -275,17 +356,17 @@ def _check_table_model(topo: Sequence[str], parents: Mapping[str, Sequence[str]]
             pm = prec.state["_class_mask"].bool()
             for k in range(int(prec.output_dim)):
                 if col >= len(pv):
-                    raise ValueError(f"categorical_table node '{n}' {_OFF_PATH}: it has {len(pv)} parent columns, "
+                    raise ValueError(f"{rec.kind} node '{n}' {_OFF_PATH}: it has {len(pv)} parent columns, "
                                      f"its parents are wider")
                 want = prec.state["_class_values"][k][pm[k]].to(torch.float32)
                 have = pv[col].to(torch.float32).reshape(-1)
                 if have.shape != want.shape or not bool((have == want).all()):
-                    raise ValueError(f"categorical_table node '{n}' {_OFF_PATH}: its support of parent '{p}' "
+                    raise ValueError(f"{rec.kind} node '{n}' {_OFF_PATH}: its support of parent '{p}' "
                                      f"(column {col}: {have.tolist()}) is not the parent's class values "
                                      f"{want.tolist()}")
                 col += 1
         if col != int(rec.input_dim):
-            raise ValueError(f"categorical_table node '{n}' {_OFF_PATH}: input_dim {rec.input_dim} != parents "
+            raise ValueError(f"{rec.kind} node '{n}' {_OFF_PATH}: input_dim {rec.input_dim} != parents "
                              f"width {col}")
 
 
@@ -343,8 +424,9 @@ def checkpoint_from_model(model: BNModel, *, seed: Optional[int] = None, device:
         extra_state = None
         if rec.kind == "kde":
             extra_state = {k: (v.clone() if isinstance(v, torch.Tensor) else v) for k, v in (rec.extra or {}).items()}
-        elif rec.kind == "categorical_table":
-            # get_extra_state (categorical_table.py:77-82): parent_values is a list of tensors
+        elif rec.kind in DISCRETE_KINDS:
+            # get_extra_state (categorical_table.py:77-82, categorical_embedded_softmax.py:121-125):
+            # parent_values is a list of tensors
             extra_state = {k: ([x.clone() for x in v] if k == "parent_values" and v is not None
                                else (list(v) if isinstance(v, (list, tuple)) else v))
                            for k, v in (rec.extra or {}).items()}
@@ -648,5 +730,52 @@ def random_table_model(g: nx.DiGraph, n_classes, seed: int = 0, *, class_values:
         cpds[node] = CPDRecord(kind="categorical_table", input_dim=len(pv), output_dim=1,
                                hparams=dict(YAML_DEFAULTS["categorical_table"], n_classes=c), state=state, extra=extra)
     model = BNModel(nodes=list(g.nodes), edges=list(g.edges), topo=topo, parents=parents, cpds=cpds)
+    _check_table_model(model.topo, model.parents, model.cpds)
+    return model
+
+
+def random_embed_model(g: nx.DiGraph, n_classes, seed: int = 0, *, embedding_dim: int = 8,
+                       hidden_dims: Sequence[int] = (64, 64), activation: str = "relu", tables: Sequence[str] = (),
+                       masked: Optional[Mapping[str, int]] = None,
+                       overrides: Optional[Mapping[str, Dict[str, Any]]] = None, gain: float = 2.0) -> BNModel:
+    """A discrete model over the DAG ``g`` with seeded random ``categorical_embedded_softmax`` CPDs
+    (no reference involved); the nodes in ``tables`` are ``categorical_table`` CPDs as
+    :func:`random_table_model` draws them.  One-dimensional nodes, ``n_classes`` an int or a
+    per-node mapping, class values 0..C-1, ``masked[node]`` trailing classes masked out.
+    Embeddings are N(0, 1) rows (nn.Embedding's init), layers nn.Linear's init with the last one
+    scaled by ``gain`` so that the softmax is not near uniform; ``overrides[node]`` replaces
+    ``embedding_dim`` / ``hidden_dims`` / ``activation`` per node."""
+    base = random_table_model(g, n_classes, seed=seed, masked=masked)
+    gen = torch.Generator().manual_seed(seed + 1)
+    cpds: Dict[str, CPDRecord] = {}
+    for node in base.topo:
+        trec = base.cpds[node]
+        if node in set(tables):
+            cpds[node] = trec
+            continue
+        hp = dict(YAML_DEFAULTS["categorical_embedded_softmax"], embedding_dim=int(embedding_dim),
+                  hidden_dims=tuple(int(h) for h in hidden_dims), activation=str(activation))
+        hp.update((overrides or {}).get(node, {}))
+        hp["hidden_dims"] = tuple(int(h) for h in hp["hidden_dims"])
+        cv, mask = trec.state["_class_values"], trec.state["_class_mask"]
+        c = int(cv.shape[1])
+        hp["n_classes"] = c
+        state = {"_class_values": cv.clone(), "_sample_values": cv.clone(), "_class_mask": mask.clone(),
+                 "_stats_ready": torch.tensor(True)}
+        pv = [v.clone() for v in trec.extra["parent_values"]]
+        cards = [int(v.numel()) for v in pv]
+        if not pv:
+            state["_logits"] = torch.randn(1, c, generator=gen) * float(gain) * 0.5
+        else:
+            e = int(hp["embedding_dim"])
+            for j, k in enumerate(cards):
+                state[f"embeddings.{j}.weight"] = torch.randn(k, e, generator=gen)
+            state.update(_mlp_state(len(pv) * e, hp["hidden_dims"], c, gen))
+            last = 2 * len(hp["hidden_dims"])
+            state[f"net.{last}.weight"] = state[f"net.{last}.weight"] * float(gain)
+        cpds[node] = CPDRecord(kind="categorical_embedded_softmax", input_dim=len(pv), output_dim=1, hparams=hp,
+                               state=state, extra={"parent_values": pv, "parent_cards": cards})
+    model = BNModel(nodes=list(base.nodes), edges=list(base.edges), topo=list(base.topo), parents=dict(base.parents),
+                    cpds=cpds)
     _check_table_model(model.topo, model.parents, model.cpds)
     return model

@@ -22,7 +22,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .plan import KM_NOISELESS, KM_TABLE, MODE_GIBBS, MODE_MCM, S_WBLK_LEN, STEP_INTS
+from .plan import KM_EMBED, KM_NOISELESS, KM_TABLE, MODE_GIBBS, MODE_MCM, S_WBLK_LEN, STEP_INTS
 
 __all__ = ["walk", "walk_segment", "table_walk", "normalize_weights", "rb_epilogue", "resample", "posterior_stats"]
 
@@ -109,24 +109,28 @@ def walk_segment(steps: Tensor, in_cols: Tensor, params: Tensor, fixed: Tensor, 
 def table_walk(steps: Tensor, in_cols: Tensor, params: Tensor, fixed: Tensor, noise: Optional[Tensor],
                out_cols: Tensor, n_queries: int, n_samples: int, n_slots: int, fixed_ld: int,
                fixed_per_particle: bool, noise_b: int, n_noise: int, dmax: int, n_out_cols: int, mode: int,
-               q_base: int, seed: int, offset: int, want_lp: bool) -> Tuple[Tensor, Tensor]:
-    """One particle walk of a plan whose every step is a categorical_table (plan.QueryPlan.tabular;
-    csrc/vbn_table_walk.hip).  ``params``: the model's whole table blob; ``out_cols``: the plan's
-    ``table_out_cols`` (slots ++ class-value offsets); the samples are class values."""
+               q_base: int, seed: int, offset: int, want_lp: bool, embed_rows: int = 0) -> Tuple[Tensor, Tensor]:
+    """One particle walk of a discrete plan (plan.QueryPlan.tabular; csrc/vbn_table_walk.hip).
+    ``params``: the model's whole table blob; ``out_cols``: the plan's ``table_out_cols`` (slots ++
+    class-value offsets); the samples are class values.  ``embed_rows`` > 0: the plan holds
+    categorical_embedded_softmax steps, whose logits need that many LDS scratch rows per wave (the
+    plan's ``max_out``); 0: every step is a categorical_table."""
     return table_walk_ex(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
-                         fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp)
+                         fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp,
+                         embed_rows)
 
 
 @table_walk.register_fake
 def _table_walk_fake(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
-                     fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp):
+                     fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp,
+                     embed_rows=0):
     total = n_queries * n_samples
     return params.new_empty(total if want_lp else 0), params.new_empty((total, n_out_cols) if n_out_cols > 0 else (0,))
 
 
 def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
                 fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp,
-                run_if=None, out_x=None):
+                embed_rows=0, run_if=None, out_x=None):
     """Checked arguments of a table walk: (VbnWalkArgs, lp, x)."""
     device = params.device
     if device.type != "cuda":
@@ -175,7 +179,7 @@ def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_sam
     a.n_samples = n_samples
     a.n_steps = int(steps.shape[0])
     a.n_slots = n_slots
-    a.max_out = 0
+    a.max_out = int(embed_rows)
     a.fixed_ld = fixed_ld
     a.fixed_per_particle = int(fixed_per_particle)
     a.noise_b = noise_b
@@ -183,7 +187,7 @@ def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_sam
     a.dmax = dmax
     a.n_out_cols = n_out_cols
     a.mode = mode
-    a.kind_mask = KM_TABLE
+    a.kind_mask = KM_TABLE | (KM_EMBED if embed_rows > 0 else 0)
     a.q_base = q_base
     a.seed = seed & ((1 << 64) - 1)
     a.offset = offset & ((1 << 64) - 1)
@@ -193,12 +197,12 @@ def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_sam
 
 
 def table_walk_ex(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
-                  fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp, *,
-                  run_if=None, out_x=None):
+                  fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp,
+                  embed_rows=0, *, run_if=None, out_x=None):
     """:func:`table_walk` as a plain launch, plus ``run_if`` / ``out_x`` as in :func:`walk_ex`."""
     a, lp, x = _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
                            fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset,
-                           want_lp, run_if, out_x)
+                           want_lp, embed_rows, run_if, out_x)
     lib = _lib.load()
     device = params.device
     with torch.cuda.device(device):
@@ -876,7 +880,8 @@ def _query_walk(plan, params, fixed, n_samples, seed, offset, q_base, noise, pla
     if secs[0] is None:
         raise ValueError("vbn_hip: plan has no walk section")
     if int(secs[0][3][8]) & KM_TABLE:
-        raise NotImplementedError("vbn_hip: the query-level ops are not implemented for categorical_table plans "
+        raise NotImplementedError("vbn_hip: the query-level ops are not implemented for categorical_table / "
+                                  "categorical_embedded_softmax plans "
                                   "(use the engines, which run them on vbn_hip::table_walk)")
     b = int(fixed.shape[0])
     if fixed.dim() != 2 or fixed.shape[1] < secs[0][3][6]:

@@ -30,7 +30,7 @@ from .model import BNModel, CPDRecord
 
 # ---- the values of include/vbn_hip_types.h and csrc/*.h (tests/test_layout_constants.py compares) ----
 KIND_ID = {"gaussian_nn": 0, "linear_gaussian": 1, "mdn": 2, "kde": 3, "softmax_nn": 4, "categorical_table": 5,
-           "rff_gaussian": 6}
+           "rff_gaussian": 6, "categorical_embedded_softmax": 7}
 # kind-set bits (VBN_KM_*): bits 0-4 = 1 << kind of every CPD kind walked (kinds 0-4), then
 KM_NONRELU = 32           # some NN CPD has a non-relu activation
 KM_HALFWAVE = 64          # half-wave launch (wave_particles 32)
@@ -39,6 +39,7 @@ KM_NOISELESS = 256        # no injected draws (production Gibbs sweeps)
 KM_GENERIC_MLP = 512      # some step runs out of line: an NN CPD with hidden_dims other than (32, 32),
                           # or an rff_gaussian node
 KM_TABLE = 1024           # kind_mask of a plan whose walked steps are all categorical_table
+KM_EMBED = 2048           # with KM_TABLE: some walked step is a categorical_embedded_softmax
 KM_KINDS = 63             # the plan's CPD kinds and KM_NONRELU
 KM_NN_KINDS = 21          # any NN kind: gaussian_nn | mdn | softmax_nn
 KM_UNSTAGED_KINDS = 28    # mdn | kde | softmax_nn: kind sets that read weights from the blob, not LDS
@@ -646,6 +647,87 @@ def _pack_table(blob: _Blob, rec: CPDRecord) -> Dict[str, int]:
     return offs
 
 
+def _acc_rows(v: np.ndarray, nblk: int) -> np.ndarray:
+    """``v [..., n]`` in MFMA accumulator row order, zero-padded: [..., nblk, half 2, 16] =
+    v[..., 32 blk + row(r, h)] -- what a lane half holds of a 32-row block (csrc/vbn_table_embed.h)."""
+    z = np.zeros(v.shape[:-1] + (nblk * 32,), np.float32)
+    z[..., :v.shape[-1]] = v
+    return np.stack([z[..., 32 * k + _ROWS] for k in range(nblk)], axis=-3)
+
+
+def embed_l1_rows(w1: np.ndarray, emb: Sequence[np.ndarray]) -> List[np.ndarray]:
+    """Layer 1 of a categorical_embedded_softmax node pre-contracted per parent column:
+    ``T_j[c] = W1[:, jE:(j+1)E] emb_j[c]`` ([card_j, H1]; float64 sums rounded to float32 once), so
+    that ``W1 concat(emb_j[idx_j]) = sum_j T_j[idx_j]``."""
+    out, at = [], 0
+    for e in emb:
+        k = e.shape[1]
+        out.append((e.astype(np.float64) @ w1[:, at:at + k].astype(np.float64).T).astype(np.float32))
+        at += k
+    return out
+
+
+def _pack_embed(blob: _Blob, rec: CPDRecord) -> Dict[str, int]:
+    """Blocks of a categorical_embedded_softmax node (csrc/vbn_table_embed.h).
+
+    A root has no network: its masked ``_logits`` become one-configuration categorical_table rows
+    (``pts`` / ``w1`` / ``w2`` of :func:`_pack_table`, in the reference's float32 ops:
+    masked_fill(-1e9), log_softmax, softmax) and the node walks as a table step.
+
+    A node with parents packs ``w1`` = b1 in accumulator row order [nb1][2][16]; ``tail`` = per
+    parent column (offset of T_j, cardinality) with T_j = [card][nb1][2][16] (:func:`embed_l1_rows`);
+    ``w2`` = the int32 table of the layers after the first [L, (in blocks, out blocks, off_w,
+    off_b) x L], off_w = A operands of v_mfma_f32_32x32x2_f32 [out blk][in blk][16 s][64 lanes] =
+    W[32 ob + (l & 31)][32 ib + row(s, l >> 5)], off_b [out blk][2][16]; all zero-padded to 32-row
+    blocks.  Both pack ``w3`` class values [D][Cp] and ``b3`` valid classes per dim as tables do."""
+    st = rec.state
+    cvs, mask = st["_class_values"].to(torch.float32), st["_class_mask"].bool()
+    d, c = (int(x) for x in cvs.shape)
+    cp = -(-c // 4) * 4
+    offs: Dict[str, int] = {}
+    cv = np.zeros((d, cp), np.float32)
+    cv[:, :c] = _np(cvs)
+    if rec.is_root:
+        logits = st["_logits"].to(torch.float32).masked_fill(~mask, -1e9)
+        logp = torch.log_softmax(logits, dim=-1)
+        exact = torch.softmax(logits, dim=-1)
+        cdf = exact.double().cumsum(dim=-1).to(torch.float32)
+
+        def rows(t: torch.Tensor, pad_last: bool = False) -> np.ndarray:
+            out = np.zeros((d, 1, cp), np.float32)
+            out[:, 0, :c] = _np(t)
+            if pad_last:
+                out[:, :, c:] = out[:, :, c - 1:c]
+            return out
+        offs.update(pts=blob.add(rows(logp)), w1=blob.add(rows(cdf, pad_last=True)), w2=blob.add(rows(exact)))
+        offs["tail"] = blob.add(np.zeros((1, 2), np.int32).view(np.float32))
+        offs["_table"] = (c, 1, cp)
+    else:
+        layers = [(_np(w), _np(b)) for w, b in rec.mlp_layers()]
+        w1, b1 = layers[0]
+        nb1 = -(-w1.shape[0] // 32)
+        emb = [_np(st[f"embeddings.{j}.weight"]) for j in range(rec.input_dim)]
+        hdr = np.zeros((rec.input_dim, 2), np.int32)
+        for j, t in enumerate(embed_l1_rows(w1, emb)):
+            hdr[j] = (blob.add(_acc_rows(t, nb1)), t.shape[0])
+        offs["tail"] = blob.add(hdr.view(np.float32))
+        offs["w1"] = blob.add(_acc_rows(b1, nb1))
+        lane = np.arange(64)
+        table = [len(layers) - 1]
+        for w, b in layers[1:]:
+            nbo, nbi = -(-w.shape[0] // 32), -(-w.shape[1] // 32)
+            wz = np.zeros((nbo * 32, nbi * 32), np.float32)
+            wz[:w.shape[0], :w.shape[1]] = w
+            frag = np.stack([np.stack([np.stack([wz[32 * ob + (lane & 31), 32 * ib + _ROWS[lane >> 5, s]]
+                                                 for s in range(16)]) for ib in range(nbi)]) for ob in range(nbo)])
+            table += [nbi, nbo, blob.add(frag), blob.add(_acc_rows(b, nbo))]
+        offs["w2"] = blob.add(np.asarray(table, np.int32).view(np.float32))
+        offs["_embed"] = (c, nb1, cp)
+    offs["w3"] = blob.add(cv)
+    offs["b3"] = blob.add(np.ascontiguousarray(mask.sum(dim=-1).to(torch.int32).numpy(), np.int32).view(np.float32))
+    return offs
+
+
 @dataclass
 class NodePack:
     kind: int
@@ -674,6 +756,15 @@ def _pack_node(blob: _Blob, rec: CPDRecord) -> NodePack:
         k, aux0, aux1 = offs.pop("_table")
         return NodePack(kind=KIND_ID[kind], flags=flags, act=0, n_in=rec.input_dim, out_dim=D, k=k, n_out=0,
                         aux0=aux0, aux1=aux1, offs=offs, scratch=0)
+    if kind == "categorical_embedded_softmax":
+        offs = _pack_embed(blob, rec)
+        if root:                                   # a one-configuration table step
+            k, aux0, aux1 = offs.pop("_table")
+            return NodePack(kind=KIND_ID["categorical_table"], flags=flags, act=0, n_in=0, out_dim=D, k=k, n_out=0,
+                            aux0=aux0, aux1=aux1, offs=offs, scratch=0)
+        k, aux0, aux1 = offs.pop("_embed")
+        return NodePack(kind=KIND_ID[kind], flags=flags, act=ACT_ID[str(rec.hp("activation"))], n_in=rec.input_dim,
+                        out_dim=D, k=k, n_out=D * k, aux0=aux0, aux1=aux1, offs=offs, scratch=D * k)
     if kind == "rff_gaussian":
         # k = the feature count; no weight block (the fragments are read from the blob); the
         # features stay in registers, the D scratch rows hold loc
@@ -825,7 +916,9 @@ class PackedModel:
         host = blob.finish()
         # an all-categorical_table model walks on vbn_hip_table_walk, which stages the whole blob
         # into LDS in 1-KiB chunks: its length is a multiple of the chunk
-        self.tabular = all(p.kind == KIND_ID["categorical_table"] for p in self.nodes.values())
+        # (so does a discrete model with categorical_embedded_softmax nodes, which never stages)
+        self.tabular = all(p.kind in (KIND_ID["categorical_table"], KIND_ID["categorical_embedded_softmax"])
+                           for p in self.nodes.values())
         if self.tabular and host.size % WBLK_CHUNK:
             host = np.concatenate([host, np.zeros((-host.size) % WBLK_CHUNK, np.float32)])
         self.params = torch.from_numpy(host).to(self.device)
@@ -859,8 +952,8 @@ class QueryPlan:
     pc: Optional["QueryPlan"] = None
     pre: Optional["QueryPlan"] = None
     pre_q: Optional["QueryPlan"] = None
-    # every walked step is a categorical_table: the plan runs on vbn_hip_table_walk (kind_mask
-    # 1024, wbuf = the blob's length, out_cols = slots ++ class-value offsets), in the model's
+    # every walked step is a categorical_table or a categorical_embedded_softmax: the plan runs on
+    # vbn_hip_table_walk (kind_mask 1024, | 2048 with embedded steps, whose logits take max_out scratch rows; wbuf = the blob's length, out_cols = slots ++ class-value offsets), in the model's
     # topological order (the log-weights add in the reference's order), without precompute plans
     tabular: bool = False
     table_out_cols: Optional[torch.Tensor] = None     # int32: out_cols ++ the columns' class-value offsets
@@ -983,7 +1076,7 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
             return 2 * model.out_dim(n)                               # loc ++ scale
         if rec.kind == "softmax_nn":
             return model.out_dim(n) * int(rec.hp("n_classes"))        # class probabilities [D][C]
-        if rec.kind == "categorical_table":
+        if rec.kind in ("categorical_table", "categorical_embedded_softmax"):
             return model.out_dim(n) * int(packed.nodes[n].k)          # class probabilities [D][C]
         if rec.kind == "mdn":
             return int(rec.hp("n_components")) * (1 + 2 * model.out_dim(n))  # weights, loc, scale
@@ -1121,7 +1214,9 @@ def build_plan(packed: PackedModel, *, latent: Sequence[str], fixed: Sequence[st
     tabular = bool(getattr(packed, "tabular", False))
     wbuf = int(steps[:, S_WBLK_LEN].max()) if len(order) else 0
     if tabular:
-        kind_mask = KM_TABLE
+        # an embedded step also maps a fixed value to its class index, so every step in the order counts
+        embedded = any(packed.nodes[n].kind == KIND_ID["categorical_embedded_softmax"] for n in order)
+        kind_mask = KM_TABLE | (KM_EMBED if embedded else 0)
         wbuf = int(packed.params.numel())
         # the table walk keeps class indices in the slots: per output column, where its class
         # values are in the blob (-1: a PARAMS column, the slot holds the probability itself)
