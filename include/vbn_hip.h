@@ -37,7 +37,10 @@
  *   vbn_hip_walk (mode GIBBS)  GibbsSampler.sample sweeps (vbn/sampling/gibbs.py:23-92):
  *                             8 candidates per chain drawn by the node's CPD, scored with the
  *                             node's and its children's log-probs, one chosen per chain
- *   vbn_hip_resample        the multinomial resampling step of
+ *   vbn_hip_table_walk (mode GIBBS)  the same sweeps on networks whose every CPD is a
+ *                             CategoricalTableCPD: draws and scores as row gathers from the
+ *                             packed tables (csrc/vbn_table_gibbs.h)
+ *   vbn_hip_resample       the multinomial resampling step of
  *                             ResampledImportanceSampling._resample
  *                               (vbn/inference/resampled_importance_sampling.py:33-41)
  *   vbn_hip_rb_epilogue     the Rao-Blackwellized mixture / categorical marginal of
@@ -80,11 +83,18 @@ int vbn_hip_walk(const vbn_walk_args* args, void* stream);
  * Node slots hold class indices; out_cols is [n_out_cols slots] ++ [n_out_cols blob offsets of
  * the columns' class values, -1 for a PARAMS column]; wbuf_floats is the length of the parameter
  * blob in floats (a multiple of 256), which the launch stages into LDS when that does not cut
- * occupancy (environment VBN_TABLE_GLOBAL=1: never).  VBN_E_ARGS for what it does not implement:
- * state / state_flags, precomp_q, stats_part, wave_particles = 32, mode GIBBS, any other
+ * occupancy (environment VBN_TABLE_GLOBAL=1: never).  An all-table walk (kind_mask 1024) may
+ * store its state: state [n_slots + 1][B*S] with state_flags = 2 receives every slot's class
+ * index (int32 bits) and the log-weight.  Mode GIBBS (kind_mask 1024 only) runs gibbs_iters
+ * sweeps of the sweep table vbn_hip_walk's mode GIBBS takes (LATENT + LPRESET, FIXED + KEEP + LOGP,
+ * SELECT, COLLECT; csrc/vbn_table_gibbs.h): it needs state with state_flags = 1 (such a stored
+ * state, every chain's column repeated for its 8 candidate lanes), n_samples = 8, gibbs_iters >
+ * gibbs_burn_in >= 0, gibbs_thin > 0 and out_x [B][n_collect][n_out_cols], which receives the
+ * target's class values; out_cols is not read.  VBN_E_ARGS for what it does not implement:
+ * loading state outside mode GIBBS, precomp_q, stats_part, wave_particles = 32, any other
  * kind_mask; vbn_hip_walk in turn refuses kind_mask 1024.  (Replaces
- * vbn/cpds/categorical_table.py:359-417 inside the engines' topological loops and
- * vbn/inference/categorical_exact.py:89-128.) */
+ * vbn/cpds/categorical_table.py:359-417 inside the engines' topological loops,
+ * vbn/inference/categorical_exact.py:89-128 and, on table networks, vbn/sampling/gibbs.py:34-87.) */
 int vbn_hip_table_walk(const vbn_walk_args* args, void* stream);
 /* 1 when vbn_hip_table_walk would stage these arguments' tables into LDS, 0 when it gathers
  * them from global memory, -(error code) for arguments it refuses. */

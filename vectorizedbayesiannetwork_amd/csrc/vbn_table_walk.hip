@@ -36,6 +36,10 @@
 // node's MLP per particle on MFMA and needs max_out rows of LDS scratch per wave for the logits.
 // It reads tables and weights from global / L2 only.  All-table plans keep the two instantiations
 // above, whose code the EMBED parameter does not touch.
+//
+// An all-table walk can store its slots (state_flags 2): that is the start state of the Gibbs
+// sweeps on table networks, vbn_table_gibbs_kernel (vbn_table_gibbs.h), which the same entry
+// launches for mode GIBBS under the same staging rule.
 #include "vbn_hip.h"
 #include "vbn_walk_common.h"
 #include "vbn_table_embed.h"
@@ -169,6 +173,14 @@ vbn_table_walk_kernel(const vbn_walk_args A, const float* __restrict__ params, c
     if (st.flags & VBN_F_LOGP) lp += node_lp;
   }
   if (!valid) return;
+  if constexpr (!EMBED) {
+    // state_flags 2: the class indices of every slot (int bits) and the log-weight, slot-major
+    // [n_slots + 1][B*S] -- the start state of the Gibbs sweeps (vbn_table_gibbs.h)
+    if (A.state && (A.state_flags & 2)) {
+      for (int c = 0; c < A.n_slots; ++c) A.state[(int64_t)c * total + L.p] = __int_as_float(idx[c * WAVE + lane]);
+      A.state[(int64_t)A.n_slots * total + L.p] = lp;
+    }
+  }
   if (A.out_lp && A.mode != VBN_MODE_SAMPLE) A.out_lp[L.p] = (A.mode == VBN_MODE_MCM) ? __expf(lp) : lp;
   if (A.out_x) {
     // out_cols = [slot per column] ++ [blob offset of the column's class values, or -1 for a
@@ -181,6 +193,8 @@ vbn_table_walk_kernel(const vbn_walk_args A, const float* __restrict__ params, c
     }
   }
 }
+
+#include "vbn_table_gibbs.h"   // mode GIBBS: vbn_table_gibbs_kernel
 
 // ------------------------------------------------------------------------------------------
 // C-ABI
@@ -214,10 +228,27 @@ static int tw_check(const vbn_walk_args* a) {
                                 "(kind_mask 1024) or a categorical_embedded_softmax (kind_mask 3072)");
   if ((a->kind_mask & VBN_KM_EMBED) && a->max_out <= 0)
     return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: an embedded plan needs max_out logit scratch rows");
-  if (a->state || a->state_flags || a->precomp_q || a->stats_part || a->wave_particles == 32 ||
-      (a->mode != VBN_MODE_MCM && a->mode != VBN_MODE_WEIGHTED && a->mode != VBN_MODE_SAMPLE))
-    return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: segment state, precomputed quantities, fused statistics, "
-                                "half waves and Gibbs sweeps are not implemented for table walks");
+  const bool gibbs = a->mode == VBN_MODE_GIBBS;
+  if (a->precomp_q || a->stats_part || a->wave_particles == 32 ||
+      (!gibbs && a->mode != VBN_MODE_MCM && a->mode != VBN_MODE_WEIGHTED && a->mode != VBN_MODE_SAMPLE))
+    return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: precomputed quantities, fused statistics and half waves "
+                                "are not implemented for table walks");
+  if (gibbs) {
+    // the sweeps of vbn_table_gibbs.h: started from a state, all-table plans only
+    if (!a->state || a->state_flags != 1 || a->n_samples != 8 || a->gibbs_iters <= 0 || a->gibbs_burn_in < 0 ||
+        a->gibbs_burn_in >= a->gibbs_iters || a->gibbs_thin <= 0 || !a->out_x || a->n_out_cols <= 0 ||
+        (a->noise && a->n_noise <= 0))
+      return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: Gibbs sweeps need a start state (state_flags 1), 8 candidates, "
+                                  "iters > burn_in >= 0, thin > 0, out_x");
+    if (a->kind_mask != VBN_KM_TABLE)
+      return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: Gibbs sweeps run all-categorical_table plans only "
+                                  "(kind_mask 1024), not categorical_embedded_softmax steps");
+  } else if (a->state || a->state_flags) {
+    // a walk may store its slots (the Gibbs start state); it does not resume from one
+    if (!a->state || a->state_flags != 2 || a->kind_mask != VBN_KM_TABLE)
+      return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: a table walk stores its state (state_flags 2, all-table "
+                                  "plans); loading segment state is not implemented for table walks");
+  }
   if (a->out_x && (!a->out_cols || a->n_out_cols <= 0))
     return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: out_x without out_cols");
   if (a->wbuf_floats <= 0 || (a->wbuf_floats % WBLK_CHUNK) != 0)
@@ -244,9 +275,23 @@ static int tw_shape(const vbn_walk_args* a, tw_launch* out) {
   const char* env_s = getenv("VBN_TABLE_STAGE");
   const bool force_stage = env_s && env_s[0] && env_s[0] != '0';
   out->nw = nw;
+  // Gibbs sweeps read the blob gibbs_iters times and their launches are small (8 chains per wave:
+  // 4096 chains are 128 workgroups), so residency costs nothing while every workgroup of the
+  // launch is resident at the staged size anyway: such a launch stages.  24 nodes, 4096 chains,
+  // 2610 sweeps, 3 of 6 workgroups per CU: 105.3 ms staged vs 115.3 ms global.
+  bool all_resident = false;
+  if (a->mode == VBN_MODE_GIBBS && staged <= TW_LDS_WG_MAX) {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) {
+      const int64_t blocks = (a->n_queries * (int64_t)a->n_samples + (int64_t)WAVE * nw - 1) / ((int64_t)WAVE * nw);
+      all_resident = blocks <= (int64_t)cus * std::min<int64_t>(TW_WG_PER_CU, TW_LDS_CU / staged);
+    }
+  }
   out->stage = !embed && !force_global && nw == TW_WAVES && staged <= TW_LDS_WG_MAX &&
-               (force_stage || std::min<int64_t>(TW_WG_PER_CU, TW_LDS_CU / staged) ==
-                                   std::min<int64_t>(TW_WG_PER_CU, TW_LDS_CU / plain));
+               (force_stage || all_resident ||
+                std::min<int64_t>(TW_WG_PER_CU, TW_LDS_CU / staged) ==
+                    std::min<int64_t>(TW_WG_PER_CU, TW_LDS_CU / plain));
   out->lds = (size_t)(out->stage ? staged : plain);
   return 0;
 }
@@ -261,7 +306,15 @@ extern "C" int vbn_hip_table_walk(const vbn_walk_args* a, void* stream) {
   const int64_t blocks = (total + (int64_t)WAVE * w.nw - 1) / ((int64_t)WAVE * w.nw);
   if (blocks > 0x7fffffffLL) return vbn_fail(VBN_E_ARGS, "vbn_hip_table_walk: too many particles for one launch");
   hipStream_t st = (hipStream_t)stream;
-  if (a->kind_mask & VBN_KM_EMBED)
+  if (a->mode == VBN_MODE_GIBBS) {
+    // lane = (chain, candidate): the same grid over n_queries x 8 lanes, the same LDS and staging rule
+    if (w.stage)
+      hipLaunchKernelGGL((vbn_table_gibbs_kernel<true>), dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
+                         a->params, a->steps, a->in_cols, a->wbuf_floats);
+    else
+      hipLaunchKernelGGL((vbn_table_gibbs_kernel<false>), dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
+                         a->params, a->steps, a->in_cols, a->wbuf_floats);
+  } else if (a->kind_mask & VBN_KM_EMBED)
     hipLaunchKernelGGL((vbn_table_walk_kernel<false, true>), dim3((unsigned)blocks), dim3(WAVE * w.nw), w.lds, st, *a,
                        a->params, a->steps, a->in_cols, a->wbuf_floats);
   else if (w.stage)

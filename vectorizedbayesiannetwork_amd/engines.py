@@ -239,8 +239,9 @@ def _check_discrete(pk: PackedModel, vals: Dict[str, torch.Tensor], nodes: Seque
 
 
 def _no_tables(vbn, what: str) -> None:
-    """Engines the table walk does not serve yet (follow-ups: they need segment state, the RB
-    epilogue or Gibbs sweeps in csrc/vbn_table_walk.hip); raised before anything touches the GPU."""
+    """Engines the table walk does not serve yet (follow-ups: they need segment state or the RB
+    epilogue in csrc/vbn_table_walk.hip; Gibbs sweeps run all-table networks behind
+    ``GibbsSampler(tables=True)`` only); raised before anything touches the GPU."""
     kinds = {rec.kind for rec in model_from_vbn(vbn).cpds.values()}
     mine = [k for k in DISCRETE_KINDS if k in kinds]
     if mine:
@@ -409,7 +410,7 @@ def run_walk(pk: PackedModel, plan: QueryPlan, fixed: torch.Tensor, b: int, n: i
         return _run_table_walk(pk, plan, fixed, b, n, seed=seed, offset=offset, q_base=q_base, noise=noise,
                                noise_b=noise_b, fixed_per_particle=fixed_per_particle, state=state,
                                run_if=run_if, out_x=out_x, stats_part=stats_part, step_begin=step_begin,
-                               step_end=step_end)
+                               step_end=step_end, state_flags=state_flags)
     pcs = _pc_state()
     if pcs["on"]:
         # VBN.precompile / pack_query: compile (or load) the specialised walk this launch would
@@ -505,10 +506,13 @@ def run_walk(pk: PackedModel, plan: QueryPlan, fixed: torch.Tensor, b: int, n: i
 
 
 def _run_table_walk(pk, plan, fixed, b, n, *, seed, offset, q_base, noise, noise_b, fixed_per_particle, state,
-                    run_if, out_x, stats_part, step_begin, step_end):
+                    run_if, out_x, stats_part, step_begin, step_end, state_flags=0):
     """run_walk for a tabular plan: one vbn_hip_table_walk launch (no generations, pre-passes or
-    plan-specialised modules; in precompile mode there is nothing to compile)."""
-    if state is not None or stats_part is not None or step_begin != 0 or step_end >= 0:
+    plan-specialised modules; in precompile mode there is nothing to compile).  ``state`` with
+    ``state_flags`` 2 (all-table plans, the whole table): the walk stores its class-index slots,
+    the start state of the table Gibbs sweeps."""
+    stores = state is not None and state_flags == 2 and not plan.kind_mask & KM_EMBED
+    if ((state is not None and not stores) or stats_part is not None or step_begin != 0 or step_end >= 0):
         raise NotImplementedError("segmented walks and fused statistics are not implemented for "
                                   "categorical_table networks")
     n_out_cols = int(plan.out_cols.numel()) if plan.out_nodes else 0
@@ -526,10 +530,10 @@ def _run_table_walk(pk, plan, fixed, b, n, *, seed, offset, q_base, noise, noise
     args = (plan.steps, plan.in_cols, pk.params, fixed, noise, plan.table_out_cols, b, n, plan.n_slots,
             plan.fixed_ld, fixed_per_particle, noise_b, len(plan.noise_nodes), pk.dmax, n_out_cols, plan.mode,
             q_base, seed, offset, want_lp, plan.max_out if plan.kind_mask & KM_EMBED else 0)
-    if run_if is None and out_x is None:
+    if run_if is None and out_x is None and state is None:
         lp, x = ops.table_walk(*args)
     else:
-        lp, x = ops.table_walk_ex(*args, run_if=run_if,
+        lp, x = ops.table_walk_ex(*args, run_if=run_if, state=state,
                                   out_x=None if out_x is None else out_x.view(b * n, n_out_cols))
     if want_lp:
         lp = lp.view(b, n)
@@ -1103,13 +1107,24 @@ class GibbsSampler(_EngineBase):
     list holds views of the chain state (gibbs.py:86), so every entry is the state after the
     LAST sweep; the walk then writes only that sweep.  ``collect="chain"`` writes the target
     at every collected sweep instead (burn-in, thinning by ``n_steps``) -- the Markov chain.
+
+    ``tables=True`` runs networks whose every CPD is a ``categorical_table`` on the table sweep
+    kernel (csrc/vbn_table_gibbs.h, through ``ops.gibbs_walk``): class indices in LDS, every term
+    of a score one row gather, class values out.  Full waves only (``wave_particles=32`` raises),
+    ``chain_waves`` / ``plan_jit`` are ignored (there is no specialised module).  A network with a
+    ``categorical_embedded_softmax`` node still raises ``NotImplementedError``; continuous
+    networks run as without the keyword.  The keyword exists only because the default behaviour
+    on discrete networks -- ``NotImplementedError`` -- is pinned by tests/test_table_model.py and
+    tests/test_embed_model.py; it is not part of ``defaults.sampling("gibbs")``.
     """
 
     HALF_WAVE_BELOW = ops.HALF_WAVE_BELOW   # ops.gibbs_walk's automatic half-wave threshold
 
     def __init__(self, n_samples: int = 200, burn_in: int = 10, n_steps: int = 1, collect: str = "reference",
-                 wave_particles: Optional[int] = None, chain_waves: Optional[int] = None, **kwargs):
+                 wave_particles: Optional[int] = None, chain_waves: Optional[int] = None, tables: bool = False,
+                 **kwargs):
         super().__init__(n_samples=n_samples, **kwargs)
+        self.tables = bool(tables)        # opt in: all-categorical_table networks on the table sweeps
         if wave_particles not in (None, 32, 64):
             raise ValueError(f"wave_particles must be None (auto), 32 or 64, got {wave_particles!r}")
         if chain_waves not in (None, *range(9)):
@@ -1144,7 +1159,16 @@ class GibbsSampler(_EngineBase):
         target, ev, do = self._query(query)
         if not target:
             raise ValueError("Gibbs sampling needs a query target")
-        _no_tables(vbn, "gibbs sampling")
+        if self.tables:
+            kinds = {rec.kind for rec in model_from_vbn(vbn).cpds.values()}
+            if "categorical_embedded_softmax" in kinds:
+                raise NotImplementedError("gibbs sampling with tables=True runs all-categorical_table networks; "
+                                          "categorical_embedded_softmax nodes are not implemented")
+            if "categorical_table" in kinds and self.wave_particles == 32:
+                raise ValueError("wave_particles=32: the table sweeps of categorical_table networks run full "
+                                 "waves only")
+        else:
+            _no_tables(vbn, "gibbs sampling")
         b = infer_batch_size(ev, do)
         dev = _device_of(vbn)
         pk = packed_model(vbn, dev)
@@ -1170,6 +1194,8 @@ class GibbsSampler(_EngineBase):
         slot, dt = init.slot_of[target], model.out_dim(target)
         if iters == 0:
             return x0[..., slot:slot + dt].contiguous()                                 # 89-91
+        if init.tabular and _pc_state()["on"]:               # nothing to compile, nothing launches
+            return torch.zeros(b, n if self.collect == "chain" and n > 0 else max(n, 1), dt, device=dev)
         if self.collect == "chain" and n > 0:
             burn, th = self.burn_in, thin
         else:

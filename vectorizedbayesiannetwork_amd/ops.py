@@ -3,6 +3,7 @@
 * ``vbn_hip::walk``               -> ``vbn_hip_walk``             (particle pass)
 * ``vbn_hip::walk_segment``       -> ``vbn_hip_walk``             (one segment of a split pass)
 * ``vbn_hip::table_walk``         -> ``vbn_hip_table_walk``       (particle pass of an all-categorical_table plan)
+* ``vbn_hip::gibbs_walk``         -> ``vbn_hip_walk`` / ``vbn_hip_table_walk`` (Gibbs sweeps; KM_TABLE plans: the table sweeps)
 * ``vbn_hip::normalize_weights``  -> ``vbn_hip_normalize_weights`` (softmax over S + ESS)
 * ``vbn_hip::rb_epilogue``        -> ``vbn_hip_rb_epilogue``       (Rao-Blackwellized target)
 * ``vbn_hip::resample``           -> ``vbn_hip_resample``          (multinomial particle resampling)
@@ -130,7 +131,7 @@ def _table_walk_fake(steps, in_cols, params, fixed, noise, out_cols, n_queries, 
 
 def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
                 fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp,
-                embed_rows=0, run_if=None, out_x=None):
+                embed_rows=0, run_if=None, out_x=None, state=None):
     """Checked arguments of a table walk: (VbnWalkArgs, lp, x)."""
     device = params.device
     if device.type != "cuda":
@@ -166,6 +167,10 @@ def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_sam
         x = out_x
     if run_if is not None:
         _check_dev("run_if", run_if, torch.int32, device)
+    if state is not None:
+        _check_dev("state", state, torch.float32, device)
+        if embed_rows > 0 or state.numel() < (n_slots + 1) * total:
+            raise ValueError(f"vbn_hip::table_walk: state needs an all-table plan and {(n_slots + 1) * total} values")
     a = _lib.VbnWalkArgs()
     a.steps = _ptr(steps)
     a.in_cols = in_cols.data_ptr()
@@ -193,16 +198,21 @@ def _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_sam
     a.offset = offset & ((1 << 64) - 1)
     a.wbuf_floats = int(params.numel())
     a.run_if = _ptr(run_if)
+    if state is not None:
+        a.state = _ptr(state)
+        a.state_flags = 2
     return a, lp, x
 
 
 def table_walk_ex(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
                   fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset, want_lp,
-                  embed_rows=0, *, run_if=None, out_x=None):
-    """:func:`table_walk` as a plain launch, plus ``run_if`` / ``out_x`` as in :func:`walk_ex`."""
+                  embed_rows=0, *, run_if=None, out_x=None, state=None):
+    """:func:`table_walk` as a plain launch, plus ``run_if`` / ``out_x`` as in :func:`walk_ex` and
+    ``state`` (float32 [n_slots + 1, B*S], all-table plans): the walk stores every slot's class index
+    (int32 bits) and the log-weight into it -- the start state of :func:`gibbs_walk`'s table sweeps."""
     a, lp, x = _table_args(steps, in_cols, params, fixed, noise, out_cols, n_queries, n_samples, n_slots, fixed_ld,
                            fixed_per_particle, noise_b, n_noise, dmax, n_out_cols, mode, q_base, seed, offset,
-                           want_lp, embed_rows, run_if, out_x)
+                           want_lp, embed_rows, run_if, out_x, state)
     lib = _lib.load()
     device = params.device
     with torch.cuda.device(device):
@@ -379,7 +389,11 @@ def gibbs_walk(steps: Tensor, in_cols: Tensor, params: Tensor, fixed: Tensor, no
     ``plan_jit`` as for :func:`walk` (0 interpreter, 1 auto, 2 always specialised).
     ``chain_waves`` (specialised sweeps only): 1..8 = chain workgroups of that many waves that
     split each sweep's node updates by level (plan.gibbs_schedule; bit-identical chains), 0 = one
-    wave per chain group, -1 = auto (chain workgroups of auto_chain_waves(groups) waves)."""
+    wave per chain group, -1 = auto (chain workgroups of auto_chain_waves(groups) waves).
+    A plan whose ``kind_mask`` has KM_TABLE runs the table sweep kernel behind
+    ``vbn_hip_table_walk`` instead (csrc/vbn_table_gibbs.h): ``state`` holds class indices (int32
+    bits, a table walk's stored state), the values returned are class values, ``params`` is the
+    whole table blob; full waves only, ``plan_jit`` / ``chain_waves`` / ``wbuf`` are not used."""
     if wave_particles not in (0, 32, 64):
         raise ValueError(f"vbn_hip::gibbs_walk: wave_particles must be 0 (auto), 32 or 64, got {wave_particles}")
     if not -1 <= chain_waves <= 8:
@@ -440,6 +454,25 @@ def gibbs_walk(steps: Tensor, in_cols: Tensor, params: Tensor, fixed: Tensor, no
     a.gibbs_thin = thin
     a.n_noise = n_noise
     a.wbuf_floats = int(wbuf)
+    if kind_mask & KM_TABLE:
+        # a discrete plan: the table sweep kernel behind vbn_hip_table_walk (csrc/vbn_table_gibbs.h);
+        # full waves, no specialised module, the whole blob as the staging length
+        if wave_particles == 32:
+            raise ValueError("vbn_hip::gibbs_walk: table sweeps run full waves only (wave_particles 0 or 64)")
+        if params.numel() % 256 or params.numel() == 0:
+            raise ValueError("vbn_hip::gibbs_walk: params must be a table blob of a multiple of 256 floats")
+        a.wbuf_floats = int(params.numel())
+        a.max_out = 0
+        a.wave_particles = 64
+        lib = _lib.load()
+        with torch.cuda.device(device):
+            LAST_WALK["table_staged"] = lib.vbn_hip_table_walk_staged(ctypes.byref(a)) == 1
+            _lib.check(lib.vbn_hip_table_walk(ctypes.byref(a), ctypes.c_void_p(_stream_handle(device))),
+                       "vbn_hip_table_walk")
+        LAST_WALK["specialised"] = False
+        LAST_WALK["chain_waves"] = 0
+        LAST_WALK["wave_particles"] = 64
+        return x
     auto_wp = wave_particles == 0
     cw = chain_waves
     if cw < 0:        # auto: chain workgroups whose LDS fits (fit_chain_waves), else the one-wave form
